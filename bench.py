@@ -9,7 +9,12 @@ ModelNet40-shaped batch [B, 2, 3, 224, 224] resident in HBM.  Workload: config
 C2 (B = 64 per GPU, bf16 trunk, training_guided gating: eps 0.01, window 5,
 gate unlocked).  N > 1: weak scaling, 64 per GPU (config C3 = 512 at 8 GPUs).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+A plain run sets up, warms up, times the steps and prints the result line (value, ms_per_step,
+config).  `--full` adds what takes runs of its own behind the timed steps: the roofline objects
+(trunk convolutions, norms+SGD pass, MMTM squeeze) and the CPU baseline.  `--dump-outputs DIR`
+writes what the last timed step computed as DIR/<name>.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full] [--dump-outputs DIR]
        torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
 """
 import argparse
@@ -55,7 +60,13 @@ def parse():
                     help="per-GPU batch (multi-view objects); default 64 (C2, C4) / 32 (C5)")
     ap.add_argument("--size", type=int, default=224)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline objects (trunk convolutions, "
+                         "norms+SGD pass, MMTM squeeze) and the CPU baseline, and add them to the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, branch logits, a fixed seeded "
+                         "sample of the updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--curate-all", action="store_true",
                     help="A/B: open a curation window longer than the run on the on-device gate before "
                          "the timed steps, so every timed step is a curated one")
@@ -65,12 +76,33 @@ def parse():
     ap.add_argument("--copy-inputs", action="store_true",
                     help="copy each step's resident batch into the engine's static input buffers (the pre-r06 "
                          "form) instead of binding the two resident batches as graph inputs")
-    ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic_group_sumsq.json"))
-    ap.add_argument("--conv-traffic-file", default=os.path.join(ROOT, "profiles", "r06g_traffic_conv_family.json"))
-    ap.add_argument("--mmtm-traffic-file", default=os.path.join(ROOT, "profiles", "r03_traffic_mmtm.json"))
+    ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic_group_sumsq.json"),
+                    help="with --full: PMC traffic (hbm_bytes_per_launch) of that roofline object")
+    ap.add_argument("--conv-traffic-file", default=os.path.join(ROOT, "profiles", "r06g_traffic_conv_family.json"),
+                    help="with --full: PMC traffic (hbm_bytes_per_launch) of that roofline object")
+    ap.add_argument("--mmtm-traffic-file", default=os.path.join(ROOT, "profiles", "r03_traffic_mmtm.json"),
+                    help="with --full: PMC traffic (hbm_bytes_per_launch) of that roofline object")
     ap.add_argument("--profile", action="store_true",
-                    help="steps only (no roofline / cpu_baseline measurements): for rocprofv3 runs")
+                    help="steps only, short line: for rocprofv3 runs")
     return ap.parse_args()
+
+
+PARAM_SAMPLE = 1 << 22  # dumped parameter values (16 MiB of fp32), fixed seeded indices
+
+
+def dump_outputs(d, step, loss):
+    """What a caller of the timed path holds after its last step: the returned loss, the step's
+    branch logits (step.last_outs) and the parameters the fused SGD pass updated - of those a
+    fixed sample (seeded indices into the flat fp32 buffer)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = step.flat.total
+    # seeded draws with replacement: constant cost whatever the model's size (C5: 12 x ResNet-50)
+    idx = np.sort(np.random.RandomState(0).randint(0, total, size=PARAM_SAMPLE))
+    np.save(os.path.join(d, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    np.save(os.path.join(d, "logits.npy"), torch.stack([o.detach().float() for o in step.last_outs]).cpu().numpy())
+    np.save(os.path.join(d, "params_sample.npy"),
+            step.flat.param[torch.from_numpy(idx).to(step.flat.param.device)].cpu().numpy())
 
 
 def cpu_baseline(seconds, size):
@@ -226,6 +258,42 @@ def dp_info(step, dist_on):
     return info
 
 
+def rooflines(a, step, conv, kern_avg_s, mmtm_bytes, mmtm_s):
+    """The `roofline*` objects of a --full line, from the timings taken behind the steps and the
+    PMC traffic files."""
+    bytes_alg = 12 * step.flat.total  # read param + grad, write param (fp32)
+    achieved = bytes_alg / kern_avg_s / 1e9
+    traffic = conv_traffic = mmtm_traffic = None
+    if os.path.exists(a.mmtm_traffic_file):
+        with open(a.mmtm_traffic_file) as f:
+            mmtm_traffic = json.load(f).get("hbm_bytes_per_launch")
+    if os.path.exists(a.conv_traffic_file):
+        with open(a.conv_traffic_file) as f:
+            conv_traffic = json.load(f).get("hbm_bytes_per_launch")
+    if os.path.exists(a.traffic_file):
+        with open(a.traffic_file) as f:
+            traffic = json.load(f).get("hbm_bytes_per_launch")
+    return {
+        "roofline": conv_roofline(conv, conv_traffic if a.dtype == "bf16" and a.workload == "C2" else None,
+                                  a.dtype, a.workload),
+        "roofline_hbm": {"kernel": "k_group_sumsq<SGD> (fused per-branch norms + SGD, gm_group_sumsq)",
+                         "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                         # the PMC traffic file is measured on C2's parameter set
+                         "traffic": traffic if a.workload == "C2" else None,
+                         "alg_bytes_per_launch": bytes_alg,
+                         "avg_launch_us": round(kern_avg_s * 1e6, 2)},
+        "roofline_mmtm": {"kernel": "k_colreduce_nhwc (MMTM squeeze: GAP of both views, site s2, "
+                                    "north-star batch 256, gm_mmtm_spatial_reduce; launches rotate over 4 "
+                                    "distinct pairs = 411 MB > 256 MiB Infinity Cache)",
+                          "bound": "hbm", "batch": 256,
+                          "achieved": round(mmtm_bytes / mmtm_s / 1e9, 1), "peak": HBM_PEAK_GBS,
+                          "unit": "GB/s", "frac": round(mmtm_bytes / mmtm_s / 1e9 / HBM_PEAK_GBS, 4),
+                          "traffic": mmtm_traffic, "alg_bytes_per_launch": mmtm_bytes,
+                          "avg_launch_us": round(mmtm_s * 1e6, 2)},
+    }
+
+
 def main():
     a = parse()
     if "RANK" not in os.environ and a.gpus > 1:
@@ -319,8 +387,8 @@ def main():
         elapsed = float(t)
     ms = 1e3 * elapsed / a.steps
     loss = float(step.last_loss)
-    # roofline kernel: the fused per-branch norms + SGD pass (k_group_sumsq<SGD>), the
-    # same launch the step runs (inside the graph), timed with HIP events on its stream
+    if a.dump_outputs and rank == 0:  # before --full's measurements: they run the SGD pass again
+        dump_outputs(a.dump_outputs, step, step.last_loss)
     if a.profile:
         if rank == 0:
             print(json.dumps({"profile_run": True, "ms_per_step": round(ms, 3), "steps": a.steps, "n_gpus": world,
@@ -329,26 +397,17 @@ def main():
         if dist_on:
             dist.destroy_process_group()
         return
-    kern_avg_s = time_group_sumsq(step, 10)
-    # the step's own launches: the view-batched trunk (vtrunk.py), all V views per launch
-    # (C2: 2 x ResNet-18, C4: 4 x ResNet-18, C5: 12 x ResNet-50); the fp32 line's one view
-    conv = time_trunk_convs(B, dev, a.dtype, G=V, arch=WL["trunk"])
-    mmtm_bytes, mmtm_s = time_mmtm_reduce(dev)
+    if a.full:
+        # roofline kernel: the fused per-branch norms + SGD pass (k_group_sumsq<SGD>), the
+        # same launch the step runs (inside the graph), timed with HIP events on its stream
+        kern_avg_s = time_group_sumsq(step, 10)
+        # the step's own launches: the view-batched trunk (vtrunk.py), all V views per launch
+        # (C2: 2 x ResNet-18, C4: 4 x ResNet-18, C5: 12 x ResNet-50); the fp32 line's one view
+        conv = time_trunk_convs(B, dev, a.dtype, G=V, arch=WL["trunk"])
+        mmtm_bytes, mmtm_s = time_mmtm_reduce(dev)
     if rank == 0:
         views = V
         total_imgs = world * B * views * a.steps
-        bytes_alg = 12 * step.flat.total  # read param + grad, write param (fp32)
-        achieved = bytes_alg / kern_avg_s / 1e9
-        traffic = conv_traffic = mmtm_traffic = None
-        if os.path.exists(a.mmtm_traffic_file):
-            with open(a.mmtm_traffic_file) as f:
-                mmtm_traffic = json.load(f).get("hbm_bytes_per_launch")
-        if os.path.exists(a.conv_traffic_file):
-            with open(a.conv_traffic_file) as f:
-                conv_traffic = json.load(f).get("hbm_bytes_per_launch")
-        if os.path.exists(a.traffic_file):
-            with open(a.traffic_file) as f:
-                traffic = json.load(f).get("hbm_bytes_per_launch")
         line = {
             "metric": "multi-view images/sec + step ms, ModelNet40 2-view MVCNN+MMTM @1/2/4/8 GPU",
             "value": round(total_imgs / elapsed, 2),
@@ -369,25 +428,10 @@ def main():
                        "hipgraph": bool(step.graphs), "device_gate": bool(step.device_gate),
                        "curation_steps_timed": curation_steps, "final_loss": round(loss, 4),
                        "dp": dp_info(step, dist_on)},
-            "roofline": conv_roofline(conv, conv_traffic if a.dtype == "bf16" and a.workload == "C2" else None,
-                                      a.dtype, a.workload),
-            "roofline_hbm": {"kernel": "k_group_sumsq<SGD> (fused per-branch norms + SGD, gm_group_sumsq)",
-                             "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                             # the PMC traffic file is measured on C2's parameter set
-                             "traffic": traffic if a.workload == "C2" else None,
-                             "alg_bytes_per_launch": bytes_alg,
-                             "avg_launch_us": round(kern_avg_s * 1e6, 2)},
-            "roofline_mmtm": {"kernel": "k_colreduce_nhwc (MMTM squeeze: GAP of both views, site s2, "
-                                        "north-star batch 256, gm_mmtm_spatial_reduce; launches rotate over 4 "
-                                        "distinct pairs = 411 MB > 256 MiB Infinity Cache)",
-                              "bound": "hbm", "batch": 256,
-                              "achieved": round(mmtm_bytes / mmtm_s / 1e9, 1), "peak": HBM_PEAK_GBS,
-                              "unit": "GB/s", "frac": round(mmtm_bytes / mmtm_s / 1e9 / HBM_PEAK_GBS, 4),
-                              "traffic": mmtm_traffic, "alg_bytes_per_launch": mmtm_bytes,
-                              "avg_launch_us": round(mmtm_s * 1e6, 2)},
         }
-        if not a.no_cpu_baseline:
+        if a.full:
+            line.update(rooflines(a, step, conv, kern_avg_s, mmtm_bytes, mmtm_s))
+        if a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.cpu_seconds, a.size)
         print(json.dumps(line), flush=True)
     if dist_on:
