@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_PKG, "libgreedymml_hip.so")
 
 GM_F32, GM_BF16 = 0, 1
 GM_NCHW, GM_NHWC = 0, 1
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 c_int, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 c_float_p = ctypes.c_void_p  # device pointers are opaque
@@ -58,6 +58,11 @@ EXPORTS = {
     "gm_mmtm_channel_scale": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "gm_gemm_f32": (c_int, [c_void_p, c_int, c_void_p]),
     "gm_gemm_set_form": (c_int, [c_int]),
+    "gm_gemm_chain_sync_bytes": (c_size_t, []),
+    "gm_gemm_f32_chain": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "gm_mmtm_excite_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                   c_void_p, c_void_p]),
+    "gm_mmtm_excite_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "gm_mmtm_running_avg": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int, c_void_p]),
     "gm_mmtm_running_avg_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
@@ -308,7 +313,7 @@ EXPORTS.update({
     "gm_maxpool2d_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 })
 
-GM_FAULT_BN_SPIN, GM_FAULT_SPLITK_SPIN = 1, 2
+GM_FAULT_BN_SPIN, GM_FAULT_SPLITK_SPIN, GM_FAULT_CHAIN_SPIN = 1, 2, 4
 
 EXPORTS.update({
     "gm_device_faults": (c_int, [ctypes.POINTER(ctypes.c_uint), c_int]),
@@ -352,14 +357,15 @@ def device_faults(clear=False):
 
 
 def check_device_faults(clear=True):
-    """Raise if an in-launch hand-off (fused BatchNorm, split-K turnstile) timed out
+    """Raise if an in-launch hand-off (fused BatchNorm, split-K turnstile, chained GEMMs) timed out
     since the last check: its outputs were poisoned with NaN instead of stale data."""
     v = device_faults(clear)
     if v:
         for hook in _fault_reset_hooks:  # e.g. re-zero split-K turnstile words left mid-hand-off
             hook()
         what = [n for b, n in ((GM_FAULT_BN_SPIN, "fused BatchNorm coefficient hand-off"),
-                               (GM_FAULT_SPLITK_SPIN, "split-K convolution turnstile")) if v & b]
+                               (GM_FAULT_SPLITK_SPIN, "split-K convolution turnstile"),
+                               (GM_FAULT_CHAIN_SPIN, "chained GEMM hand-off")) if v & b]
         raise GreedyMMLError(f"device fault 0x{v:x}: {', '.join(what) or 'unknown'} timed out "
                              "(grid not co-resident?); the affected outputs are NaN")
 

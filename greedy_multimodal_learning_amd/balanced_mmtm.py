@@ -119,39 +119,45 @@ def _mmtm_forward(ctx, xv, xs, w_sq, b_sq, w_sq_v, b_sq_v, w_sq_s, b_sq_s, w_v, 
         Cz = w_sq.shape[0]
         z_v = torch.empty(B, Cz, **f32)
         z_s = z_v
-        ops.gemm([dict(M=B, N=Cz, segs=[(C2, Op(sq, C2, 1), Op(w_sq, 1, C2))], C=z_v, ld_c=Cz,
-                       bias=b_sq, act=1)], dev)
+        fc1 = [dict(M=B, N=Cz, segs=[(C2, Op(sq, C2, 1), Op(w_sq, 1, C2))], C=z_v, ld_c=Cz,
+                    bias=b_sq, act=1)]
     elif mode == TURNOFF:
         Cz = w_sq.shape[0]
         avg_v, avg_s = cfg["avg_v"], cfg["avg_s"]
         z_v, z_s = torch.empty(B, Cz, **f32), torch.empty(B, Cz, **f32)
-        ops.gemm([
+        fc1 = [
             dict(M=B, N=Cz, segs=[(Cv, Op(sq, C2, 1), Op(w_sq, 1, C2)),
                                   (Cs, Op(avg_s, 0, 1), Op(w_sq, 1, C2, off=Cv))],
                  C=z_v, ld_c=Cz, bias=b_sq, act=1),
             dict(M=B, N=Cz, segs=[(Cv, Op(avg_v, 0, 1), Op(w_sq, 1, C2)),
                                   (Cs, Op(sq, C2, 1, off=Cv), Op(w_sq, 1, C2, off=Cv))],
-                 C=z_s, ld_c=Cz, bias=b_sq, act=1)], dev)
+                 C=z_s, ld_c=Cz, bias=b_sq, act=1)]
     else:
         Cz = w_sq_v.shape[0]
         z_v, z_s = torch.empty(B, Cz, **f32), torch.empty(B, Cz, **f32)
-        ops.gemm([
+        fc1 = [
             dict(M=B, N=Cz, segs=[(Cv, Op(sq, C2, 1), Op(w_sq_v, 1, Cv))], C=z_v, ld_c=Cz,
                  bias=b_sq_v, act=1),
             dict(M=B, N=Cz, segs=[(Cs, Op(sq, C2, 1, off=Cv), Op(w_sq_s, 1, Cs))], C=z_s,
-                 ld_c=Cz, bias=b_sq_s, act=1)], dev)
+                 ld_c=Cz, bias=b_sq_s, act=1)]
     # ---- excite: e_m = sigmoid(W_m z_m + b_m)
     wv_, bv_ = (w_v, b_v)
     ws_, bs_ = (w_v, b_v) if share else (w_s, b_s)
     e_v, e_s = torch.empty(B, Cv, **f32), torch.empty(B, Cs, **f32)
-    ops.gemm([dict(M=B, N=Cv, segs=[(Cz, Op(z_v, Cz, 1), Op(wv_, 1, Cz))], C=e_v, ld_c=Cv,
-                   bias=bv_, act=2),
-              dict(M=B, N=Cs, segs=[(Cz, Op(z_s, Cz, 1), Op(ws_, 1, Cz))], C=e_s, ld_c=Cs,
-                   bias=bs_, act=2)], dev)
+    fc2 = [dict(M=B, N=Cv, segs=[(Cz, Op(z_v, Cz, 1), Op(wv_, 1, Cz))], C=e_v, ld_c=Cv,
+                bias=bv_, act=2),
+           dict(M=B, N=Cs, segs=[(Cz, Op(z_s, Cz, 1), Op(ws_, 1, Cz))], C=e_s, ld_c=Cs,
+                bias=bs_, act=2)]
     # ---- running averages (both from e_v: reference quirk) + step, in place with
     # the step counter in device memory (graph-capturable)
     ra_v, ra_s = cfg["ra_v"], cfg["ra_s"]
-    ops.running_avg_dev(e_v, ra_v, ra_s, cfg["step_dev"])
+    fused = cfg.get("excite", "chain") == "fused"
+    if fused:  # one launch: fc1 -> hand-off -> fc2 -> running average (gm_mmtm_excite_fwd)
+        ops.mmtm_excite_fwd(fc1, fc2, dev, ra_v, ra_s, cfg["step_dev"])
+    else:
+        ops.gemm(fc1, dev)
+        ops.gemm(fc2, dev)
+        ops.running_avg_dev(e_v, ra_v, ra_s, cfg["step_dev"])
     # ---- effective scales (curation substitutes the running average)
     cur, caring = cfg["curation"], cfg["caring"]
     sv, ld_sv, live_v = e_v, Cv, True
@@ -176,7 +182,7 @@ def _mmtm_forward(ctx, xv, xs, w_sq, b_sq, w_sq_v, b_sq_v, w_sq_s, b_sq_s, w_v, 
     ctx.params = {"w_sq": w_sq, "b_sq": b_sq, "w_sq_v": w_sq_v, "b_sq_v": b_sq_v, "w_sq_s": w_sq_s,
                   "b_sq_s": b_sq_s, "w_v": w_v, "b_v": b_v, "w_s": w_s, "b_s": b_s}
     ctx.meta = (B, Cv, Cs, Cz, HWv, HWs, lay, dt, mode, share, live_v, live_s,
-                ld_sv, ld_ss, cfg.get("avg_v"), cfg.get("avg_s"), cfg["zero_curated"], gate, ra_v, ra_s)
+                ld_sv, ld_ss, cfg.get("avg_v"), cfg.get("avg_s"), cfg["zero_curated"], gate, ra_v, ra_s, fused)
     ctx.mark_non_differentiable(e_v, e_s, sq)
     ctx.set_materialize_grads(False)  # no zero-filled grads for the side outputs
     return yv, ys, e_v, e_s, sq
@@ -185,7 +191,7 @@ def _mmtm_forward(ctx, xv, xs, w_sq, b_sq, w_sq_v, b_sq_v, w_sq_s, b_sq_s, w_v, 
 def _mmtm_backward(ctx, gyv, gys, outs=None):
     (xv, xs, sq, z_v, z_s, e_v, e_s, sv, ss, w_sq, w_sq_v, w_sq_s, wv_, ws_) = ctx.saved_tensors
     (B, Cv, Cs, Cz, HWv, HWs, lay, dt, mode, share, live_v, live_s,
-     ld_sv, ld_ss, avg_v, avg_s, zero_curated, gate, ra_v, ra_s) = ctx.meta
+     ld_sv, ld_ss, avg_v, avg_s, zero_curated, gate, ra_v, ra_s, fused) = ctx.meta
     dev = xv.device
     f32 = dict(device=dev, dtype=torch.float32)
     C2 = Cv + Cs
@@ -206,11 +212,11 @@ def _mmtm_backward(ctx, gyv, gys, outs=None):
             raise RuntimeError(f"MMTM {key}: in-place gradient buffer must be a contiguous {shape}")
         return torch.empty(*shape, **f32)
 
-    def gemm_acc(problems):
+    def mark_acc(problems):
         for q in problems:
             if acc_of.get(id(q["C"])):
                 q["accumulate"] = 1
-        ops.gemm(problems, dev)
+        return problems
     if gyv is None:
         gyv = torch.zeros_like(xv)
     if gys is None:
@@ -265,8 +271,7 @@ def _mmtm_backward(ctx, gyv, gys, outs=None):
             dz_s = torch.empty(B, Cz, **f32)
             probs.append(dict(M=B, N=Cz, segs=[(Cs, Op(da_s, Cs, 1), Op(ws_, Cz, 1))], C=dz_s,
                               ld_c=Cz, mask=z_s, ld_mask=Cz))
-    if probs:
-        gemm_acc(probs)
+    first = mark_acc(probs)
     # ---- squeeze FC grads + dsq
     probs = []
     dsq = None
@@ -308,8 +313,13 @@ def _mmtm_backward(ctx, gyv, gys, outs=None):
                       dict(M=1, N=Cz, segs=[(B, ONES, Op(dz, Cz, 1))], C=g["b_sq_" + key], ld_c=Cz),
                       dict(M=B, N=C, segs=[(Cz, Op(dz, Cz, 1), Op(w, C, 1))], C=dsq, c_off=off,
                            ld_c=C2)]
-    if probs:
-        gemm_acc(probs)
+    second = mark_acc(probs)
+    if fused and first and second:  # one launch: round 2 reads round 1's dz (gm_mmtm_excite_bwd)
+        ops.mmtm_excite_bwd(first, second, dev)
+    else:
+        for probs in (first, second):
+            if probs:
+                ops.gemm(probs, dev)
     # ---- dX_m = dY_m * s_m + dsq_m / HW
     dxv, dxs = (torch.empty_like(xv), torch.empty_like(xs)) if outs is None else outs
     pv = dict(x=gyv, y=dxv, C=Cv, HW=HWv, s=sv, ld_s=ld_sv)
@@ -377,6 +387,10 @@ class MMTM_mitigate(nn.Module):
         # True: host flags drive the same select/mask kernels as the device gate (the
         # test that pins the device gate against the host gate bit for bit)
         self.mask_curation = False
+        # the site's FC work: "chain" - separate launches (squeeze FC, excite FCs, running
+        # average; backward: excite gradients + dz, squeeze gradients + dsq); "fused" - one
+        # launch each way (gm_mmtm_excite_fwd / gm_mmtm_excite_bwd), bit-identical results
+        self.excite_form = "chain"
 
     def _gate_for(self, curation_mode, caring_modality, dev):
         if self.device_gate is not None or not self.mask_curation:
@@ -439,7 +453,9 @@ class MMTM_mitigate(nn.Module):
         if self.running_avg_weight_skeleton.data_ptr() == self.running_avg_weight_visual.data_ptr():
             self.running_avg_weight_skeleton = self.running_avg_weight_skeleton.clone()
         step_dev = _step_counter(self, dev)
-        cfg = dict(layout=lay, mode=mode, share=self.shareweight, step_dev=step_dev,
+        if self.excite_form not in ("chain", "fused"):
+            raise ValueError(f"MMTM excite_form must be 'chain' or 'fused' (got {self.excite_form!r})")
+        cfg = dict(layout=lay, mode=mode, share=self.shareweight, step_dev=step_dev, excite=self.excite_form,
                    ra_v=self.running_avg_weight_visual,
                    ra_s=self.running_avg_weight_skeleton,
                    curation=bool(curation_mode), caring=caring_modality,

@@ -2,7 +2,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "gm_common.h"
+#include "gemm_tile.h"
 
 namespace gm {
 
@@ -48,7 +48,7 @@ extern "C" int gm_device_faults(unsigned* out, int clear) {
         gm::set_error("gm_device_faults: %s", hipGetErrorString(e));
         return (int)e;
     }
-    *out = gm::bn_faults_read(clear != 0) | gm::conv_faults_read(clear != 0);
+    *out = gm::bn_faults_read(clear != 0) | gm::conv_faults_read(clear != 0) | gm::chain_faults_read(clear != 0);
     return GM_OK;
 }
 

@@ -15,13 +15,9 @@
 //   * fused epilogue: bias, relu / sigmoid, relu-backward mask, accumulate.
 #include <cstring>
 
-#include "gm_common.h"
+#include "gemm_tile.h"
 
 namespace gm {
-
-constexpr int kMaxGemm = 6;
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 
 struct GemmArgs {
     gm_gemm p[kMaxGemm];
@@ -32,223 +28,23 @@ struct GemmArgs {
     int vec;  // 1: the float4 K-segment form where the operands allow it (A/B knob)
 };
 
-// One K-segment of a wave's 16x16 tile: k in [k0, k1) (segment-local), stepping 4.
-// Lane (li, lk) reads A[m0+li][k+lk] and B[k+lk][n0+li]; pointers advance by
-// 4*ld1 / 4*ld0 per step.  8 steps (32 k) per iteration with the next
-// iteration's 16 loads issued before this iteration's 8 MFMAs (register
-// double-buffer), so L2 latency hides behind MFMA issue.  Every load is
-// unconditional from a clamped, in-range address and the validity select comes
-// after it: a "load or constant" select on a per-lane condition makes hipcc branch
-// around each load with a vmcnt(0) inside (cdna_hip_programming.md §5 trap 4c),
-// i.e. one dependent L2 round trip per k-step.
-template <int U>
-__device__ __forceinline__ void seg_mma(floatx4& acc, const gm_operand& A, const gm_operand& B,
-                                        int m, int n, bool mrow, bool ncol, int lk, int k0, int k1) {
-    if (k1 <= k0) return;
-    const bool aone = A.ptr == nullptr;
-    // an all-ones A operand loads (and ignores) B's in-range elements
-    const float* pa = aone ? B.ptr : A.ptr + (long)m * A.ld0 + (long)(k0 + lk) * A.ld1;
-    const float* pb = B.ptr + (long)(k0 + lk) * B.ld0 + (long)n * B.ld1;
-    const long sa = aone ? 0 : 4l * A.ld1, sb = 4l * B.ld0;
-    const bool va = mrow && !aone, vb = ncol;
-    const float one = mrow ? 1.0f : 0.0f;
-    int k = k0;
-    if (k + 4 * U <= k1) {
-        float ac[U], bc[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            ac[u] = pa[u * sa];
-            bc[u] = pb[u * sb];
-        }
-        for (; k + 8 * U <= k1; k += 4 * U) {
-            float an[U], bn[U];
-            const float* qa = pa + U * sa;
-            const float* qb = pb + U * sb;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                an[u] = qa[u * sa];
-                bn[u] = qb[u * sb];
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(va ? ac[u] : one, vb ? bc[u] : 0.f, acc, 0, 0, 0);
-#pragma unroll
-            for (int u = 0; u < U; ++u) { ac[u] = an[u]; bc[u] = bn[u]; }
-            pa = qa;
-            pb = qb;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(va ? ac[u] : one, vb ? bc[u] : 0.f, acc, 0, 0, 0);
-        k += 4 * U;
-        pa += U * sa;
-        pb += U * sb;
-    }
-    // tail (< 4U k): lanes past k1 re-read the segment's last k and contribute zero
-    for (; k < k1; k += 4) {
-        const bool in = (k + lk) < k1;
-        const long back = in ? 0 : (long)(k + lk - (k1 - 1));
-        const float al = pa[-back * (aone ? 0 : A.ld1)];
-        const float bl = pb[-back * B.ld0];
-        const float av = in ? (va ? al : (aone ? one : 0.f)) : 0.f;
-        const float bv = (in && vb) ? bl : 0.f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-        pa += sa;
-        pb += sb;
-    }
-}
-
-// The same K-segment on 16-k groups with 16-byte loads along k where an operand is
-// k-contiguous (A.ld1 == 1 / B.ld0 == 1, 16-B aligned rows): the four MFMAs of a group
-// take k = kg + 4*lk + q in MFMA q (any k -> (lane, instruction) assignment is valid
-// when A and B agree), so lane lk's float4 at kg + 4*lk feeds all four; a k-strided
-// operand loads its four scalars at those same k.  A strided fp32 load touches one
-// cache line per lane row for 4 B of it: the float4 form asks the TA for 4x fewer lines.
-// UG groups (16*UG k) per load round, the next round in flight under this one's MFMAs.
-template <bool VA, bool VB, int UG>
-__device__ __forceinline__ void seg_mma_v(floatx4& acc, const gm_operand& A, const gm_operand& B, int m, int n,
-                                          bool mrow, bool ncol, int lk, int k0, int k1) {
-    const bool aone = A.ptr == nullptr;
-    const bool va = mrow && !aone, vb = ncol;
-    const float one = mrow ? 1.0f : 0.0f;
-    const float* pa = aone ? B.ptr : A.ptr + (long)m * A.ld0;
-    const float* pb = B.ptr + (long)n * B.ld1;
-    const long sa = aone ? 0 : A.ld1, sb = B.ld0;
-    auto load = [&](int kg, float (&a)[4], float (&b)[4]) {
-        const int k = kg + 4 * lk;
-        if constexpr (VA) {
-            const float4 t = *reinterpret_cast<const float4*>(pa + k);
-            a[0] = t.x; a[1] = t.y; a[2] = t.z; a[3] = t.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a[q] = pa[(long)(k + q) * sa];
-        }
-        if constexpr (VB) {
-            const float4 t = *reinterpret_cast<const float4*>(pb + k);
-            b[0] = t.x; b[1] = t.y; b[2] = t.z; b[3] = t.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) b[q] = pb[(long)(k + q) * sb];
-        }
-    };
-    auto mma = [&](const float (&a)[4], const float (&b)[4]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(va ? a[q] : one, vb ? b[q] : 0.f, acc, 0, 0, 0);
-    };
-    int kg = k0;
-    if (kg + 16 * UG <= k1) {
-        float ac[UG][4], bc[UG][4];
-#pragma unroll
-        for (int g = 0; g < UG; ++g) load(kg + 16 * g, ac[g], bc[g]);
-        for (; kg + 32 * UG <= k1; kg += 16 * UG) {
-            float an[UG][4], bn[UG][4];
-#pragma unroll
-            for (int g = 0; g < UG; ++g) load(kg + 16 * (UG + g), an[g], bn[g]);
-#pragma unroll
-            for (int g = 0; g < UG; ++g) mma(ac[g], bc[g]);
-#pragma unroll
-            for (int g = 0; g < UG; ++g)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { ac[g][q] = an[g][q]; bc[g][q] = bn[g][q]; }
-        }
-#pragma unroll
-        for (int g = 0; g < UG; ++g) mma(ac[g], bc[g]);
-        kg += 16 * UG;
-    }
-    for (; kg + 16 <= k1; kg += 16) {
-        float a[4], b[4];
-        load(kg, a, b);
-        mma(a, b);
-    }
-    if (kg < k1) seg_mma<4>(acc, A, B, m, n, mrow, ncol, lk, kg, k1);  // < 16 k left
-}
-
-// one K-segment: the float4 form where the operands allow it (uniform per problem)
-template <int U>
-__device__ __forceinline__ void seg_any(int vec, floatx4& acc, const gm_operand& A, const gm_operand& B, int m,
-                                        int n, bool mrow, bool ncol, int lk, int k0, int k1) {
-    if (k1 <= k0) return;
-    const bool va4 = A.ptr != nullptr && A.ld1 == 1 && (A.ld0 & 3) == 0 && ((uintptr_t)A.ptr & 15) == 0;
-    const bool vb4 = B.ld0 == 1 && (B.ld1 & 3) == 0 && ((uintptr_t)B.ptr & 15) == 0;
-    if (vec == 0 || (!va4 && !vb4)) seg_mma<U>(acc, A, B, m, n, mrow, ncol, lk, k0, k1);
-    else if (va4 && vb4) seg_mma_v<true, true, U / 4>(acc, A, B, m, n, mrow, ncol, lk, k0, k1);
-    else if (va4) seg_mma_v<true, false, U / 4>(acc, A, B, m, n, mrow, ncol, lk, k0, k1);
-    else seg_mma_v<false, true, U / 4>(acc, A, B, m, n, mrow, ncol, lk, k0, k1);
-}
-
-// GEMM forms (gm_gemm_set_waves A/B knob): waves per workgroup x k-steps per load round
-struct GemmForm { int nw, u; };
-// forms 4 / 5: timing diagnostics of form 1 (outputs meaningless): arguments and one
-// store only / everything but the operand loads and MFMAs
-constexpr GemmForm kForms[] = {{4, 8}, {4, 16}, {8, 16}, {16, 8}};
-static int g_gemm_form = 1, g_gemm_vec = 1, g_gemm_outer = 1;
+// GEMM forms (gm_gemm_set_form A/B knob, kForms in gemm_tile.h)
+static GemmKnobs g_knobs = {1, 1, 1};
+const GemmKnobs& gemm_knobs() { return g_knobs; }
 
 // The MMTM GEMMs are dependent-latency chains (kernel arguments -> operand loads ->
 // MFMAs -> epilogue loads -> store), not MFMA work: every round trip costs ~1-2 us.  So
 // the problem index is the grid's y (no tile-table lookup before the argument loads),
 // the epilogue's operands (bias, relu mask, accumulated C) are loaded together with the
-// first operand round, and a wave's K range is at most two load rounds.
+// first operand round, and a wave's K range is at most two load rounds.  The tile's
+// arithmetic is gemm_tile (gemm_tile.h), shared with k_gemm_chain.
 template <int NW, int U>
 __global__ __launch_bounds__(NW * 64) void k_gemm_f32(GemmArgs a) {
     __shared__ floatx4 red[NW][64];
     const int pi = blockIdx.y;
-    const gm_gemm& p = a.p[pi];
-    const int cfg = a.cfg[pi];
-    const int TM = cfg & 31, TN = (cfg >> 5) & 31, KS = (cfg >> 10) & 31;
     const int wg = blockIdx.x;
     if (wg >= a.tile_start[pi + 1] - a.tile_start[pi]) return;
-    const int wm = wg / a.tiles_n[pi], wn = wg - wm * a.tiles_n[pi];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int tile = wave / KS, ks = wave - tile * KS;
-    const int tm = tile / TN, tn = tile - tm * TN;
-    const int m0 = (wm * TM + tm) * 16, n0 = (wn * TN + tn) * 16;
-    const int li = lane & 15, lk = lane >> 4;
-    const int K0 = p.K[0], Ktot = p.K[0] + p.K[1];
-    // K range of this split (global k, a multiple of 16 per split)
-    const int k16 = (Ktot + 15) >> 4;
-    const int per = (k16 + KS - 1) / KS;
-    const int kb = min(Ktot, ks * per * 16), ke = min(Ktot, (ks + 1) * per * 16);
-    const bool mrow = (m0 + li) < p.M, ncol = (n0 + li) < p.N;
-    const int mm = mrow ? m0 + li : 0, nn = ncol ? n0 + li : 0;
-    // epilogue operands, in flight with the first operand round (clamped addresses)
-    float bias = 0.f, mk[4] = {1.f, 1.f, 1.f, 1.f}, co[4] = {0.f, 0.f, 0.f, 0.f};
-    if (ks == 0) {
-        if (p.bias) bias = p.bias[nn];
-        if (p.mask) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mk[r] = p.mask[(size_t)min(m0 + lk * 4 + r, p.M - 1) * p.ld_mask + nn];
-        }
-        if (p.accumulate) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) co[r] = p.C[(size_t)min(m0 + lk * 4 + r, p.M - 1) * p.ld_c + nn];
-        }
-    }
-    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-    seg_any<U>(a.vec, acc, p.A[0], p.B[0], mm, nn, mrow, ncol, lk, kb, min(ke, K0));
-    if (p.K[1] > 0)
-        seg_any<U>(a.vec, acc, p.A[1], p.B[1], mm, nn, mrow, ncol, lk, max(kb, K0) - K0, ke - K0);
-    if (KS > 1) {
-        red[wave][lane] = acc;
-        __syncthreads();
-        if (ks != 0) return;
-        for (int s = 1; s < KS; ++s) {
-            const floatx4 o = red[wave + s][lane];
-            acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2]; acc[3] += o[3];
-        }
-    }
-    // C/D map of 16x16x4: col = lane&15, row = (lane>>4)*4 + r
-    const int n = n0 + li;
-    if (n >= p.N) return;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int m = m0 + lk * 4 + r;
-        float v = acc[r] + bias;
-        if (p.act == 1) v = relu_nan(v);
-        else if (p.act == 2) v = 1.0f / (1.0f + expf(-v));
-        v = mk[r] > 0.f ? v : 0.f;
-        if (m < p.M) p.C[(size_t)m * p.ld_c + n] = co[r] + v;
-    }
+    gemm_tile<NW, U>(a.p[pi], a.cfg[pi], a.tiles_n[pi], wg, a.vec, red, false);
 }
 
 // ---------------------------------------------------------------------------------
@@ -361,6 +157,22 @@ static bool outer_ok(const gm_gemm& p) {
            (p.ld_c & 3) == 0 && ((uintptr_t)p.C & 15) == 0;
 }
 
+bool gemm_takes_outer(const gm_gemm& p) {
+    return g_knobs.outer && p.M >= 1 && p.N >= 1 && p.C && p.ld_c >= p.N && p.A[0].ptr && p.B[0].ptr && outer_ok(p);
+}
+
+int gemm_check(const gm_gemm& p, int i) {
+    GM_REQUIRE(p.M >= 1 && p.N >= 1 && p.K[0] >= 0 && p.K[1] >= 0 && p.K[0] + p.K[1] >= 1,
+               "gemm_f32[%d]: bad shape M=%d N=%d K=%d+%d", i, p.M, p.N, p.K[0], p.K[1]);
+    GM_REQUIRE(p.C && p.ld_c >= p.N, "gemm_f32[%d]: bad C / ld_c", i);
+    GM_REQUIRE(p.act >= 0 && p.act <= 2, "gemm_f32[%d]: bad act %d", i, p.act);
+    GM_REQUIRE(!p.mask || p.ld_mask >= p.N, "gemm_f32[%d]: bad ld_mask", i);
+    for (int s = 0; s < 2; ++s)
+        if (p.K[s] > 0)
+            GM_REQUIRE(p.B[s].ptr, "gemm_f32[%d]: segment %d has no B operand", i, s);
+    return GM_OK;
+}
+
 }  // namespace gm
 
 using namespace gm;
@@ -379,7 +191,7 @@ extern "C" int gm_gemm_f32(const gm_gemm* in, int nprob, void* stream) {
     int nout = 0, maxt = 0;
     for (int i = 0; i < nprob; ++i) {
         const gm_gemm& p = in[i];
-        if (g_gemm_outer && p.M >= 1 && p.N >= 1 && p.C && p.ld_c >= p.N && p.A[0].ptr && p.B[0].ptr && outer_ok(p)) {
+        if (gemm_takes_outer(p)) {
             o.p[nout] = p;
             o.tiles_m[nout] = (p.M + kOM - 1) / kOM;
             const int t = o.tiles_m[nout] * ((p.N + kON - 1) / kON);
@@ -408,39 +220,20 @@ static int launch_gemm_f32(const gm_gemm* in, int nprob, hipStream_t st) {
     int tiles = 0, maxt = 0;
     for (int i = 0; i < nprob; ++i) {
         const gm_gemm& p = in[i];
-        GM_REQUIRE(p.M >= 1 && p.N >= 1 && p.K[0] >= 0 && p.K[1] >= 0 && p.K[0] + p.K[1] >= 1,
-                   "gemm_f32[%d]: bad shape M=%d N=%d K=%d+%d", i, p.M, p.N, p.K[0], p.K[1]);
-        GM_REQUIRE(p.C && p.ld_c >= p.N, "gemm_f32[%d]: bad C / ld_c", i);
-        GM_REQUIRE(p.act >= 0 && p.act <= 2, "gemm_f32[%d]: bad act %d", i, p.act);
-        GM_REQUIRE(!p.mask || p.ld_mask >= p.N, "gemm_f32[%d]: bad ld_mask", i);
-        for (int s = 0; s < 2; ++s)
-            if (p.K[s] > 0)
-                GM_REQUIRE(p.B[s].ptr, "gemm_f32[%d]: segment %d has no B operand", i, s);
+        const int rc = gemm_check(p, i);
+        if (rc) return rc;
         a.p[i] = p;
-        const int Kt = p.K[0] + p.K[1];
-        // K splits: about two load rounds (8U k) per wave, at most the workgroup's waves
-        const GemmForm f = kForms[g_gemm_form];
-        const int NW = f.nw;
-        int KS = 1;
-        while (KS < NW && KS * 8 * f.u < Kt) KS *= 2;
-        const int mt16 = (p.M + 15) / 16, nt16 = (p.N + 15) / 16;
-        int TM = 1, TN = 1;
-        while (TM * TN * KS < NW) {
-            if (TN < nt16 && (TN <= TM || TM >= mt16)) TN *= 2;
-            else if (TM < mt16) TM *= 2;
-            else TN *= 2;
-        }
-        const int tm = (p.M + 16 * TM - 1) / (16 * TM), tn = (p.N + 16 * TN - 1) / (16 * TN);
-        a.cfg[i] = TM | (TN << 5) | (KS << 10);
-        a.tiles_n[i] = tn;
+        const TilePlan t = plan_tiles(p, kForms[g_knobs.form]);
+        a.cfg[i] = t.cfg;
+        a.tiles_n[i] = t.tiles_n;
         a.tile_start[i] = tiles;
-        tiles += tm * tn;
-        if (tm * tn > maxt) maxt = tm * tn;
+        tiles += t.tiles;
+        if (t.tiles > maxt) maxt = t.tiles;
     }
     a.tile_start[nprob] = tiles;
-    a.vec = g_gemm_vec;
+    a.vec = g_knobs.vec;
     const dim3 grid(maxt, nprob);
-    switch (g_gemm_form) {
+    switch (g_knobs.form) {
         case 0: k_gemm_f32<4, 8><<<grid, 256, 0, st>>>(a); break;
         case 1: k_gemm_f32<4, 16><<<grid, 256, 0, st>>>(a); break;
         case 2: k_gemm_f32<8, 16><<<grid, 512, 0, st>>>(a); break;
@@ -450,11 +243,11 @@ static int launch_gemm_f32(const gm_gemm* in, int nprob, hipStream_t st) {
 }
 
 extern "C" int gm_gemm_set_form(int form) {
-    g_gemm_vec = !(form & 256);    // bit 8: scalar k-steps only
-    g_gemm_outer = !(form & 512);  // bit 9: no outer-product kernel (every problem on k_gemm_f32)
+    g_knobs.vec = !(form & 256);    // bit 8: scalar k-steps only
+    g_knobs.outer = !(form & 512);  // bit 9: no outer-product kernel (every problem on k_gemm_f32)
     form &= 255;
     GM_REQUIRE(form >= 0 && form < (int)(sizeof(kForms) / sizeof(kForms[0])), "gemm form must be 0..3 (got %d)",
                form);
-    g_gemm_form = form;
+    g_knobs.form = form;
     return GM_OK;
 }

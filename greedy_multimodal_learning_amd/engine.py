@@ -257,7 +257,8 @@ class GradBuckets:
 class BalancedStep:
     def __init__(self, model, lr=0.1, gate=None, compute_dtype=torch.bfloat16, channels_last=True,
                  process_group=None, bucket_mb=25.0, branchnames=("net_view_0", "net_view_1"),
-                 MMTMnames=("visual", "skeleton"), graphs=False, device_gate=None, dp_buckets=None):
+                 MMTMnames=("visual", "skeleton"), graphs=False, device_gate=None, dp_buckets=None,
+                 mmtm_excite=None):
         self.model = model
         self.lr = float(lr)
         self.gate = gate
@@ -352,6 +353,14 @@ class BalancedStep:
         from .balanced_mmtm import MMTM_mitigate
         from .mmtm_n import MMTM_N
         self._mmtms = [m for m in model.modules() if isinstance(m, (MMTM_mitigate, MMTM_N))]
+        # mmtm_excite ("chain" / "fused"; None keeps the modules' own setting): the form of the
+        # MMTM sites' FC work (MMTM_mitigate.excite_form)
+        if mmtm_excite is not None:
+            if mmtm_excite not in ("chain", "fused"):
+                raise ValueError(f"mmtm_excite must be 'chain' or 'fused' (got {mmtm_excite!r})")
+            for m in self._mmtms:
+                if isinstance(m, MMTM_mitigate):
+                    m.excite_form = mmtm_excite
         # on-device gate: the Strong gate's decision made by a kernel behind
         # the norms+SGD pass and consumed by the MMTM kernels from device memory, so no
         # host sync per step and one graph for every curation setting

@@ -135,15 +135,7 @@ class Op:
 ONES = Op(None, 0, 0)
 
 
-def gemm(problems, device):
-    """problems: list of dict(M, N, segs=[(K, Op A, Op B)], C, c_off, ld_c, bias, act, mask,
-    ld_mask, accumulate). C[m,n] (+)= act(sum_seg A.B + bias) * (mask > 0).
-    Problems must be independent (no problem reads another's output)."""
-    if len(problems) > MAX_GEMM:
-        for i in range(0, len(problems), MAX_GEMM):
-            gemm(problems[i:i + MAX_GEMM], device)
-        return
-    lib = L.load()
+def _gemm_array(problems):
     items = []
     for p in problems:
         segs = p["segs"]
@@ -155,8 +147,67 @@ def gemm(problems, device):
         items.append(L.Gemm(p["M"], p["N"], K, A, Bm, L.ptr(p.get("bias")), L.ptr(p.get("mask")),
                             p.get("ld_mask", 0), Ct.data_ptr() + 4 * p.get("c_off", 0), p["ld_c"],
                             p.get("act", 0), int(p.get("accumulate", 0))))
-    arr = L.arr(L.Gemm, items)
-    L.check(lib.gm_gemm_f32(arr, len(items), L.stream_of(device)), "gm_gemm_f32")
+    return L.arr(L.Gemm, items)
+
+
+def gemm(problems, device):
+    """problems: list of dict(M, N, segs=[(K, Op A, Op B)], C, c_off, ld_c, bias, act, mask,
+    ld_mask, accumulate). C[m,n] (+)= act(sum_seg A.B + bias) * (mask > 0).
+    Problems must be independent (no problem reads another's output)."""
+    if len(problems) > MAX_GEMM:
+        for i in range(0, len(problems), MAX_GEMM):
+            gemm(problems[i:i + MAX_GEMM], device)
+        return
+    lib = L.load()
+    arr = _gemm_array(problems)
+    L.check(lib.gm_gemm_f32(arr, len(problems), L.stream_of(device)), "gm_gemm_f32")
+
+
+_chain_sync = {}  # (device, stream) -> the chained GEMMs' sync words (zeroed once, self re-arming)
+
+
+def chain_sync(device):
+    """Device pointer of the current stream's sync words for the chained-GEMM entry points."""
+    from .streams import zeroed_scratch
+    need = L.load().gm_gemm_chain_sync_bytes()
+    return zeroed_scratch(_chain_sync, torch.device(device), need, lambda old: need).data_ptr()
+
+
+@L.on_fault_reset
+def _reset_chain_sync():
+    """A hand-off that timed out can leave an arrival counter mid-count: zero the words."""
+    for buf in _chain_sync.values():
+        buf.zero_()
+    torch.cuda.synchronize()
+
+
+def gemm_chain(first, second, device):
+    """Two dependent rounds of gemm() problems in one launch (gm_gemm_f32_chain): every problem
+    of `second` may read any output of `first`; 1..MAX_GEMM problems per round.  Bit-identical
+    to gemm(first) followed by gemm(second)."""
+    lib = L.load()
+    a1, a2 = _gemm_array(first), _gemm_array(second)
+    L.check(lib.gm_gemm_f32_chain(a1, len(first), a2, len(second), chain_sync(device), L.stream_of(device)),
+            "gm_gemm_f32_chain")
+
+
+def mmtm_excite_fwd(fc1, fc2, device, ra_v=None, ra_s=None, step_dev=None, increment=True):
+    """The MMTM site's FC chain in one launch (gm_mmtm_excite_fwd): fc1 (relu problems), then
+    fc2 (sigmoid problems) and, with ra_v, the in-place running-average update from fc2[0]'s
+    output (running_avg_dev's arithmetic and device step counter)."""
+    lib = L.load()
+    a1, a2 = _gemm_array(fc1), _gemm_array(fc2)
+    L.check(lib.gm_mmtm_excite_fwd(a1, len(fc1), a2, len(fc2), L.ptr(ra_v), L.ptr(ra_s), L.ptr(step_dev),
+                                   int(increment), chain_sync(device), L.stream_of(device)), "gm_mmtm_excite_fwd")
+
+
+def mmtm_excite_bwd(first, second, device):
+    """The MMTM site's FC backward in one launch (gm_mmtm_excite_bwd): the excite-FC gradients
+    and dz, then the squeeze-FC gradients and dsq."""
+    lib = L.load()
+    a1, a2 = _gemm_array(first), _gemm_array(second)
+    L.check(lib.gm_mmtm_excite_bwd(a1, len(first), a2, len(second), chain_sync(device), L.stream_of(device)),
+            "gm_mmtm_excite_bwd")
 
 
 def running_avg(e_v, ra_v, ra_s, step):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GM_ABI_VERSION 3
+#define GM_ABI_VERSION 4
 
 /* activation element types */
 #define GM_F32  0
@@ -46,8 +46,9 @@ extern "C" {
 int gm_abi_version(void);
 const char* gm_last_error(void);
 
-/* In-launch hand-off health.  The single-launch BatchNorm kernels and the split-K
- * convolution turnstile hand data between workgroups of one launch through a spin on
+/* In-launch hand-off health.  The single-launch BatchNorm kernels, the split-K
+ * convolution turnstile and the chained GEMMs (gm_gemm_f32_chain, gm_mmtm_excite_fwd /
+ * _bwd) hand data between workgroups of one launch through a spin on
  * a device word, bounded by a poll budget.  A spin that runs out (a grid that was not
  * co-resident after all, or a broken hand-off) never hangs and never applies stale
  * data: it sets a bit in a sticky device fault word and poisons its output with NaN.
@@ -56,6 +57,7 @@ const char* gm_last_error(void);
  * 1<<24; a test hook).  Not graph-capturable (gm_device_faults synchronises). */
 #define GM_FAULT_BN_SPIN     1u
 #define GM_FAULT_SPLITK_SPIN 2u
+#define GM_FAULT_CHAIN_SPIN  4u
 int gm_device_faults(unsigned* out, int clear);
 int gm_set_spin_limit(unsigned polls);
 /* Co-residency of the single-launch BatchNorm: at most `n` such launches are assumed
@@ -73,7 +75,8 @@ int gm_bn_set_concurrency(int n);
  *                RCCL all-reduce kernels that overlap backward under data parallelism
  * The BatchNorm grid is capped at (CUs - reserved) x (blocks per CU) /
  * (max(concurrency, streams) x sharers) and the waiting split-K workgroups of one launch at
- * (CUs - reserved) x 2 / (streams x sharers).  Defaults: 2, 1, 0.
+ * (CUs - reserved) x 2 / (streams x sharers); the chained GEMMs' persistent grid at
+ * (CUs - reserved) / (streams x sharers).  Defaults: 2, 1, 0.
  * The engine sets it per process (engine.BalancedStep).  gm_get_residency reads it. */
 int gm_set_residency(int streams, int sharers, int reserved_cus);
 int gm_get_residency(int* streams, int* sharers, int* reserved_cus);
@@ -166,6 +169,41 @@ int gm_gemm_f32(const gm_gemm* p, int nprob, void* stream);
  * 0 = 4 x 8, 1 = 4 x 16 (default), 2 = 8 x 16, 3 = 16 x 8; + 256: no float4 k-segments.
  * Process-wide. */
 int gm_gemm_set_form(int form);
+
+/* ---------------------------------------------------------------------------
+ * Two dependent rounds of gm_gemm problems in ONE launch: every problem of `second` may
+ * read any output of `first` (the MMTM site's FC chain and its backward; each separate
+ * gm_gemm_f32 launch is a ~7 us latency chain).  A persistent grid of at most
+ * (CUs - reserved) / (streams x sharers) workgroups (gm_set_residency) walks the first
+ * round's tiles, meets at a device counter and walks the second round's.  Tiles, K splits
+ * and the order of every fmaf / MFMA are gm_gemm_f32's, so the outputs are bit-identical
+ * to gm_gemm_f32(first) followed by gm_gemm_f32(second).  1..6 problems per round.
+ *
+ * sync: gm_gemm_chain_sync_bytes() bytes of device memory, zeroed ONCE by the caller and
+ * then owned by launches that are ordered on one stream (one buffer per stream).  The
+ * words re-arm themselves: back-to-back launches and graph replays need no reset.  After
+ * gm_device_faults() reports GM_FAULT_CHAIN_SPIN (a workgroup gave up waiting; its
+ * second-round and running-average outputs are NaN) the caller zeroes them again.
+ *
+ * Where the single launch cannot run - the residency plan leaves it no workgroup, or a
+ * problem is one gm_gemm_f32 gives to its outer-product kernel (one K segment <= 128 with
+ * M x N >= 2^20) - the entry point issues the separate launches itself: the call computes
+ * the same result either way.  Arguments are checked (GM_E_ARG) before anything is launched.
+ *
+ * gm_mmtm_excite_fwd: fc1 = the squeeze FC(s) (act 1: relu), fc2 = the excite FCs (act 2:
+ * sigmoid); ra_v != NULL also runs gm_mmtm_running_avg_dev(fc2[0].C, fc2[0].ld_c, fc2[0].M,
+ * fc2[0].N, ra_v, ra_s, step, increment) in the same launch (same arithmetic and order;
+ * ra_s may equal ra_v; the step counter is advanced once, after every read of it).
+ * gm_mmtm_excite_bwd: first = the excite-FC gradients and dz, second = the squeeze-FC
+ * gradients and dsq (`accumulate`, masks and strided views as in gm_gemm_f32).
+ * ------------------------------------------------------------------------- */
+size_t gm_gemm_chain_sync_bytes(void);
+int gm_gemm_f32_chain(const gm_gemm* first, int nfirst, const gm_gemm* second, int nsecond,
+                      void* sync, void* stream);
+int gm_mmtm_excite_fwd(const gm_gemm* fc1, int nfc1, const gm_gemm* fc2, int nfc2,
+                       float* ra_v, float* ra_s, int* step, int increment, void* sync, void* stream);
+int gm_mmtm_excite_bwd(const gm_gemm* first, int nfirst, const gm_gemm* second, int nsecond,
+                       void* sync, void* stream);
 
 /* ---------------------------------------------------------------------------
  * MMTM running averages (src/balanced_mmtm.py:113-116), reference quirk kept:
