@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_PKG, "libgreedymml_hip.so")
 
 GM_F32, GM_BF16 = 0, 1
 GM_NCHW, GM_NHWC = 0, 1
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 c_int, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 c_float_p = ctypes.c_void_p  # device pointers are opaque
@@ -381,7 +381,6 @@ EXPORTS.update({
 })
 
 EXPORTS.update({
-    "gm_conv_set_pipe": (c_int, [c_int]),
     "gm_conv_set_halo": (c_int, [c_int]),
     "gm_conv_set_h9": (c_int, [c_int]),
     "gm_conv_set_wgrad_staging": (c_int, [c_int]),

@@ -34,7 +34,7 @@ def test_chain_entry_points_declared_and_exported():
         assert hasattr(ctypes.CDLL(L.LIB_PATH), name), name
     assert "#define GM_FAULT_CHAIN_SPIN  4u" in hdr
     assert L.GM_FAULT_CHAIN_SPIN == 4
-    assert L.ABI_VERSION == 4 and lib.gm_abi_version() == 4
+    assert L.ABI_VERSION == 5 and lib.gm_abi_version() == 5  # (the chain: since 4; 5 removed gm_conv_set_pipe)
     n = lib.gm_gemm_chain_sync_bytes()
     assert n >= 8 and n % 16 == 0
 

@@ -359,11 +359,12 @@ HALO_SHAPES = [  # N, C, H, W, K: 3x3 / stride 1 / pad 1 (ResNet layers 2-4 and 
 ]
 
 
-@pytest.mark.parametrize("mode", [1, 2], ids=["halo128", "halo256"])
+@pytest.mark.parametrize("mode", [1, 2, 3], ids=["halo128", "halo256", "h9off"])
 @pytest.mark.parametrize("shape", HALO_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_conv_halo_tiles(dev, shape, mode):
-    """The halo-staged kernel in its 128- and 256-pixel tile forms (gm_conv_set_halo 1 / 2)
-    vs fp32 PyTorch: forward and the stride-1 input gradient."""
+    """The halo-staged kernel in its 128- and 256-pixel tile forms (gm_conv_set_halo 1 / 2), and the
+    128-pixel form with run-time tap decode (k_conv_halo<128>: gm_conv_set_h9(0), mode 3), vs fp32
+    PyTorch: forward and the stride-1 input gradient."""
     from greedy_multimodal_learning_amd import _lib as L
     from greedy_multimodal_learning_amd import conv as G
     N, C, H, W, K = shape
@@ -376,8 +377,9 @@ def test_conv_halo_tiles(dev, shape, mode):
     yr.backward(gy.float())
     cl = torch.channels_last
     lib = L.load()
-    L.check(lib.gm_conv_set_halo(mode), "gm_conv_set_halo")
     try:
+        L.check(lib.gm_conv_set_halo(1 if mode == 3 else mode), "gm_conv_set_halo")
+        L.check(lib.gm_conv_set_h9(0 if mode == 3 else 1), "gm_conv_set_h9")
         xd, wd = x.to(dev).contiguous(memory_format=cl), w.to(dev).contiguous(memory_format=cl)
         y = G.conv_fwd(xd, wd, 1, 1)
         wt = wd.permute(1, 0, 2, 3).contiguous(memory_format=cl)
@@ -386,6 +388,7 @@ def test_conv_halo_tiles(dev, shape, mode):
         assert L.device_faults(clear=True) == 0
     finally:
         lib.gm_conv_set_halo(1)
+        lib.gm_conv_set_h9(1)
     _close(y, yr, 1e-2)
     _close(dx, xr.grad, 1e-2)
 

@@ -1,6 +1,6 @@
 """Run ONE trunk convolution shape repeatedly (for rocprofv3 --pmc passes):
 
-    python tools/conv_one.py --shape l2 --op fwd --pipe 0 --reps 50
+    python tools/conv_one.py --shape l2 --op fwd --reps 50
 """
 import argparse
 import os
@@ -21,7 +21,6 @@ def main():
     ap.add_argument("--op", default="fwd", choices=["fwd", "dgrad", "wgrad"])
     ap.add_argument("--groups", type=int, default=2, help="wgrad: views per grouped launch")
     ap.add_argument("--ring", type=int, default=None, help="wgrad: gm_conv_set_wgrad_loop mode")
-    ap.add_argument("--pipe", type=int, default=-1)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--sets", type=int, default=1, help="grouped stem/wgrad: distinct operand sets cycled")
@@ -37,7 +36,6 @@ def main():
     w = torch.randn(K, C, R, R, device=dev).bfloat16().contiguous(memory_format=CL)
     dy = torch.randn(B, K, P, Q, device=dev).bfloat16().contiguous(memory_format=CL)
     wt = w.permute(1, 0, 2, 3).contiguous(memory_format=CL)
-    L.check(L.load().gm_conv_set_pipe(a.pipe), "set_pipe")
     fn = (lambda: G.conv_fwd(x, w, st, pad)) if a.op == "fwd" else (lambda: G.conv_dgrad_t(dy, wt, H, W, st, pad))
     if a.shape == "conv1" and a.op == "fwd":  # the pixel-pair stem, grouped as in the step
         fns = [T._make_bf16("fwd", B, dev, C, H, W, K, R, st, pad, P, Q, a.groups) for _ in range(a.sets)]
@@ -50,7 +48,7 @@ def main():
         B = B * a.groups
     t = T._time(fn, a.reps)
     flops = 2.0 * B * P * Q * K * C * R * R
-    print(f"{a.shape} {a.op} pipe {a.pipe}: {t * 1e6:.2f} us, {flops / t / 1e12:.1f} TFLOP/s", flush=True)
+    print(f"{a.shape} {a.op}: {t * 1e6:.2f} us, {flops / t / 1e12:.1f} TFLOP/s", flush=True)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,6 @@
 
 ARMSET: layout      - flat parameter layout: model.grad_order vs reverse registration order
         gemm_outer  - the outer-product GEMM kernel on vs off (gm_gemm_set_form bit 9)
-        pipe        - k_conv_igemm_ut main loop: PIPE 2 (default) vs PIPE 0 (gm_conv_set_pipe)
         bind        - resident batches bound as graph inputs vs copied into the static buffers (bench args)
         wgrad_batch - weight-gradient launches handed to the side stream in batches of 8 / 4 / 2
         stem_wgrad  - the stem weight gradient forming its dy from the BN + pool backward's operands
@@ -38,10 +37,6 @@ def arms(name):
         def setg(form):
             L.check(L.load().gm_gemm_set_form(form), "gemm form")
         return [("outer_on", lambda: setg(1)), ("outer_off", lambda: setg(1 | 512))]
-    if name == "pipe":
-        def setp(p):
-            L.check(L.load().gm_conv_set_pipe(p), "pipe")
-        return [("pipe2", lambda: setp(-1)), ("pipe0", lambda: setp(0))]
     if name == "stem_wgrad":
         from greedy_multimodal_learning_amd import vtrunk
 
