@@ -9,7 +9,8 @@ forward and backward run on libgreedymml_hip.so for every HIP input:
   * fp32 (the reference's own arithmetic: src/framework.py:146-148 feeds fp32
     tensors with no autocast): `gm_conv2d_f32` fwd / dgrad / wgrad on the exact-f32
     MFMA (v_mfma_f32_32x32x2_f32), activations channels_last fp32, any channel
-    count (the RGB stem unpadded).
+    count (the RGB stem unpadded); with `GMConv2d.f32_terms` = 3 or 6 the same three
+    passes run `gm_conv2d_f32_split` (split-bf16 contraction on the bf16 MFMA).
 
 Weight gradients come back in fp32 in the parameter's layout (or are written in
 place through the gradient sink).  There is no vendor-library path: a CPU tensor
@@ -443,15 +444,51 @@ def _use_hip(x):
 
 # ---- reference-precision (fp32) path ------------------------------------------------
 
-def conv_f32(mode, d, x=None, w=None, dy=None, out=None, addend=None, accumulate=False):
+F32_CONTRACTIONS = {"exact": 0, "bf16x3": 3, "bf16x6": 6}  # name -> terms
+
+
+def f32_terms_of(name):
+    """terms of an fp32 contraction mode: None / 'exact' -> 0, 'bf16x3' -> 3, 'bf16x6' -> 6."""
+    if name is None:
+        return 0
+    if name not in F32_CONTRACTIONS:
+        raise ValueError(f"f32_contraction must be None or one of {sorted(F32_CONTRACTIONS)}, got {name!r}")
+    return F32_CONTRACTIONS[name]
+
+
+def set_f32_contraction(model, name, compute_dtype):
+    """Validate an fp32 contraction mode and set it on every GMConv2d of `model` (the
+    engine at construction, the evaluation loop before its pass).  None leaves the
+    modules as they are; any mode needs compute_dtype float32.  Returns the term count."""
+    terms = f32_terms_of(name)
+    if name is None:
+        return terms
+    if compute_dtype != torch.float32:
+        raise ValueError(f"f32_contraction={name!r} needs compute_dtype=torch.float32 (got {compute_dtype})")
+    for m in model.modules():
+        if isinstance(m, GMConv2d):
+            m.f32_terms = terms
+    return terms
+
+
+def conv_f32(mode, d, x=None, w=None, dy=None, out=None, addend=None, accumulate=False, terms=0):
     """One gm_conv2d_f32 call (mode L.GM_CONV_FWD / _DGRAD / _WGRAD) on channels_last
-    fp32 tensors; `out` must be preallocated in its NHWC / KRSC layout."""
+    fp32 tensors; `out` must be preallocated in its NHWC / KRSC layout.  terms = 0: the
+    exact-f32 MFMA; 3 / 6: gm_conv2d_f32_split (bf16x3 / bf16x6 on the bf16 MFMA)."""
     lib = L.load()
     p = L.ConvF32(mode, d, L.ptr(x), L.ptr(w), L.ptr(dy), L.ptr(out), L.ptr(addend), int(accumulate), 0)
-    need = lib.gm_conv2d_f32_scratch(ctypes.byref(p))
     dev = out.device
+    if terms == 0:
+        need = lib.gm_conv2d_f32_scratch(ctypes.byref(p))
+        scratch = torch.empty(max(need, 16), device=dev, dtype=torch.uint8) if need else None
+        L.check(lib.gm_conv2d_f32(ctypes.byref(p), L.ptr(scratch), need, L.stream_of(dev)), "gm_conv2d_f32")
+        return out
+    if terms not in (3, 6):
+        raise ValueError(f"conv_f32: terms must be 0 (exact), 3 (bf16x3) or 6 (bf16x6), got {terms!r}")
+    need = lib.gm_conv2d_f32_split_scratch(ctypes.byref(p), terms)
     scratch = torch.empty(max(need, 16), device=dev, dtype=torch.uint8) if need else None
-    L.check(lib.gm_conv2d_f32(ctypes.byref(p), L.ptr(scratch), need, L.stream_of(dev)), "gm_conv2d_f32")
+    L.check(lib.gm_conv2d_f32_split(ctypes.byref(p), terms, L.ptr(scratch), need, L.stream_of(dev)),
+            "gm_conv2d_f32_split")
     return out
 
 
@@ -462,15 +499,16 @@ def _f32_cl(t):
 
 class _ConvF32Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, stride, pad, join=None):
+    def forward(ctx, x, weight, stride, pad, join=None, terms=0):
         ctx.join = join
+        ctx.terms = terms
         xc = _f32_cl(x)
         wk = _f32_cl(weight.detach())  # KRSC (a no-op for the engine's channels_last parameters)
         N, C, H, W = xc.shape
         K, _, R, S = wk.shape
         P, Q = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
         y = torch.empty(N, K, P, Q, device=xc.device, dtype=torch.float32, memory_format=CL)
-        conv_f32(L.GM_CONV_FWD, _desc(N, H, W, C, K, R, S, stride, pad), x=xc, w=wk, out=y)
+        conv_f32(L.GM_CONV_FWD, _desc(N, H, W, C, K, R, S, stride, pad), x=xc, w=wk, out=y, terms=terms)
         ctx.save_for_backward(xc, wk, weight)
         ctx.meta = (stride, pad)
         return y
@@ -479,6 +517,7 @@ class _ConvF32Fn(torch.autograd.Function):
     def backward(ctx, gy):
         xc, wk, weight = ctx.saved_tensors
         stride, pad = ctx.meta
+        terms = ctx.terms  # one mode for the layer's three passes
         gy = _f32_cl(gy)
         N, C, H, W = xc.shape
         K, _, R, S = wk.shape
@@ -489,20 +528,20 @@ class _ConvF32Fn(torch.autograd.Function):
                 out = torch.empty(N, C, H, W, device=gy.device, dtype=torch.float32, memory_format=CL)
                 if add is not None:
                     add = _f32_cl(add)
-                return conv_f32(L.GM_CONV_DGRAD, d, w=wk, dy=gy, out=out, addend=add)
+                return conv_f32(L.GM_CONV_DGRAD, d, w=wk, dy=gy, out=out, addend=add, terms=terms)
             dx = ctx.join.contribute(dgrad) if ctx.join is not None else dgrad(None)
         if ctx.needs_input_grad[1]:
             tgt = sink_target(weight)
             if tgt is not None:
                 if not (tgt[0].is_contiguous(memory_format=CL) and tgt[0].dtype == torch.float32):
                     raise RuntimeError("GMConv2d: in-place gradient buffer must be fp32 channels_last")
-                conv_f32(L.GM_CONV_WGRAD, d, x=xc, dy=gy, out=tgt[0], accumulate=tgt[1])
+                conv_f32(L.GM_CONV_WGRAD, d, x=xc, dy=gy, out=tgt[0], accumulate=tgt[1], terms=terms)
                 sink_done(weight)
             else:
                 dw = torch.empty(K, C, R, S, device=gy.device, dtype=torch.float32, memory_format=CL)
-                conv_f32(L.GM_CONV_WGRAD, d, x=xc, dy=gy, out=dw)
+                conv_f32(L.GM_CONV_WGRAD, d, x=xc, dy=gy, out=dw, terms=terms)
                 dw = _like_param(dw, weight)
-        return dx, dw, None, None, None
+        return dx, dw, None, None, None, None
 
 
 class GMConv2d(nn.Conv2d):
@@ -510,6 +549,9 @@ class GMConv2d(nn.Conv2d):
     square stride/padding, dilation 1 - the ResNet trunk's convolutions)."""
 
     pair_stem = True
+    # fp32 inputs: 0 = exact-f32 MFMA, 3 / 6 = split-bf16 contraction (bf16x3 / bf16x6) for
+    # this layer's fwd, dgrad and wgrad alike; set per module (BalancedStep(f32_contraction=))
+    f32_terms = 0
 
     def _hip_ok(self):
         return (self.groups == 1 and self.bias is None and self.dilation == (1, 1)
@@ -536,7 +578,7 @@ class GMConv2d(nn.Conv2d):
             else:
                 grad_join = None
             if not bf16:
-                return _ConvF32Fn.apply(x, self.weight, self.stride[0], self.padding[0], grad_join)
+                return _ConvF32Fn.apply(x, self.weight, self.stride[0], self.padding[0], grad_join, self.f32_terms)
             if self.uses_pair_stem() and not x.requires_grad:
                 if grad_join is not None:  # never: the stem input needs no gradient
                     raise RuntimeError("GMConv2d: pair stem with a gradient join")

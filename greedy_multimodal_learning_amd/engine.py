@@ -258,11 +258,17 @@ class BalancedStep:
     def __init__(self, model, lr=0.1, gate=None, compute_dtype=torch.bfloat16, channels_last=True,
                  process_group=None, bucket_mb=25.0, branchnames=("net_view_0", "net_view_1"),
                  MMTMnames=("visual", "skeleton"), graphs=False, device_gate=None, dp_buckets=None,
-                 mmtm_excite=None):
+                 mmtm_excite=None, f32_contraction=None):
         self.model = model
         self.lr = float(lr)
         self.gate = gate
         self.compute_dtype = compute_dtype
+        # f32_contraction (None / "exact" / "bf16x3" / "bf16x6"): how the fp32 trunk's
+        # convolutions contract (conv.py, GMConv2d.f32_terms), set on every GMConv2d here,
+        # before any graph capture; None leaves the modules' own setting
+        from .conv import set_f32_contraction
+        set_f32_contraction(model, f32_contraction, compute_dtype)
+        self.f32_contraction = f32_contraction
         self.channels_last = channels_last
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if process_group is not None else 1

@@ -18,7 +18,7 @@ import os
 import torch
 
 from .gin_lite import _CONFIG, configurable
-from .train import _DTYPES, construct_callbacks, evaluate, gin_main, save_history
+from .train import _DTYPES, construct_callbacks, evaluate, f32_contraction_arg, gin_main, save_history
 
 
 def load_pretrained(model, path):
@@ -34,10 +34,14 @@ def load_pretrained(model, path):
 @configurable
 def evalution_loop(model, loss_function, metrics, config, save_path, test=None, test_steps=None, use_gpu=True,
                    device_numbers=[0], custom_callbacks=[], pretrained_weights_path=None, save_with_structure=False,
-                   nummodalities=2, compute_dtype="fp32"):
+                   nummodalities=2, compute_dtype="fp32", f32_contraction="exact"):
     """Reference src/training_loop.py:161-200 (one evaluation epoch, `test_*` keys).
     Runs in fp32 by default (the reference's arithmetic: its recorded averages feed the
-    turn-off evaluation)."""
+    turn-off evaluation); `f32_contraction` ('exact', 'bf16x3', 'bf16x6') is set on every
+    GMConv2d as the engine sets it (fp32 only)."""
+    from .conv import set_f32_contraction
+    cdt = _DTYPES[compute_dtype]
+    set_f32_contraction(model, f32_contraction_arg(cdt, f32_contraction), cdt)
     dev = torch.device("cuda", device_numbers[0])
     if pretrained_weights_path:
         load_pretrained(model, pretrained_weights_path)

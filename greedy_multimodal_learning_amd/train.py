@@ -23,6 +23,8 @@ The loop keeps the reference's per-epoch history keys (`loss`, `acc`,
 Arithmetic: `training_loop.compute_dtype` defaults to 'fp32', the reference's own precision,
 so a reference gin config reproduces the reference's logits and CUR numbers (north_star:
 1e-4); bind `training_loop.compute_dtype = 'bf16'` for the fast (benchmarked) trunk.
+`training_loop.f32_contraction` ('exact' by default; 'bf16x3' / 'bf16x6') picks how the fp32
+trunk's convolutions contract ("fp32 contraction modes").
 
 CLI (reference: `train.py save_path configs/x.gin [bindings]`, src/utils.py:58-68):
     python -m greedy_multimodal_learning_amd.train SAVE_PATH CONFIG[#CONFIG...] [BINDINGS]
@@ -41,6 +43,15 @@ from .gin_lite import _CONFIG, configurable, parse_config_files_and_bindings
 from .losses import acc, blend_loss  # noqa: F401  (reference train.py exports both)
 
 _DTYPES = {"bf16": torch.bfloat16, "fp32": torch.float32}
+
+
+def f32_contraction_arg(compute_dtype, f32_contraction):
+    """The gin key `f32_contraction` ('exact' by default, 'bf16x3', 'bf16x6') as the
+    engine's argument: the default says nothing about a bf16 run (None), every other
+    combination is the engine's to accept or refuse."""
+    if compute_dtype != torch.float32 and f32_contraction == "exact":
+        return None
+    return f32_contraction
 
 
 def construct_callbacks(names):
@@ -113,7 +124,7 @@ def save_history(H, save_path, save_with_structure=True):
 def training_loop(model, loss_function, metrics, optimizer, config, save_path, steps_per_epoch, train=None,
                   valid=None, test=None, test_steps=None, validation_steps=None, use_gpu=True, device_numbers=[0],
                   custom_callbacks=[], checkpoint_monitor="val_acc", n_epochs=100, verbose=True, nummodalities=2,
-                  compute_dtype="fp32", graphs=True):
+                  compute_dtype="fp32", graphs=True, f32_contraction="exact"):
     """Reference src/training_loop.py:86-143 + Model_.train_loop (src/framework.py:
     250-330) on the fused engine.  `optimizer` is the (lr, momentum, wd) triple of the
     reference's SGD (only momentum = wd = 0, as every config uses, is fused; a torch SGD
@@ -141,7 +152,8 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
         raise ValueError("at most one gating callback")
     gate = gates[0] if gates else None
     cdt = _DTYPES[compute_dtype]
-    step = BalancedStep(model, lr=lr, gate=gate, compute_dtype=cdt, channels_last=True, graphs=graphs)
+    step = BalancedStep(model, lr=lr, gate=gate, compute_dtype=cdt, channels_last=True, graphs=graphs,
+                        f32_contraction=f32_contraction_arg(cdt, f32_contraction))
     # the reference's optimizer object (never stepped: the engine's fused pass applies the
     # update with the learning rate read from it)
     opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=wd)

@@ -556,6 +556,16 @@ typedef struct gm_conv_f32 {
 size_t gm_conv2d_f32_scratch(const gm_conv_f32* p);
 int gm_conv2d_f32(const gm_conv_f32* p, void* scratch, size_t scratch_bytes, void* stream);
 
+/* The same convolutions, same descriptor and same scratch size, contracted on the bf16
+ * MFMA from fp32 operands split into bf16 parts (x = h + m + l, each rounded to nearest
+ * even): terms = 3 (bf16x3: ah*bh + ah*bm + am*bh, error ~10x exact fp32) or terms = 6
+ * (bf16x6: adds ah*bl + al*bh + am*bm, error at exact fp32's level).  Any other terms is
+ * GM_E_ARG.  Deterministic.  A non-finite input gives a non-finite output, which may be
+ * NaN where the exact entry gives +-inf; |x| within one bf16 ulp of FLT_MAX is out of
+ * range. */
+size_t gm_conv2d_f32_split_scratch(const gm_conv_f32* p, int terms);
+int gm_conv2d_f32_split(const gm_conv_f32* p, int terms, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------
  * BatchNorm2d (torchvision ResNet trunk, reference src/model.py:65-106 through
  * torchvision.models.resnet18), NHWC bf16 activations x[M][C] (M = N*H*W), fp32

@@ -11,6 +11,7 @@ fraction of its own roofline bound = min(MFMA peak, arithmetic intensity x HBM p
 (peaks: MI355X_MICROARCH.md, 2.5 PFLOP/s dense bf16, 8 TB/s HBM3E).
 
     python tools/trunk_table.py [--batch 64] [--md out.md] [--reps 10]
+    python tools/trunk_table.py --f32 [--batch 64] [--rounds 5] [--md out.md]   (fp32 trunk: exact / bf16x3 / bf16x6)
 
 Also imported by bench.py (`measure_family`) for the `roofline` object, and run under
 `rocprofv3 --pmc` by tools/gpu.sh (pmc_trunk:*) so counters can be attributed per
@@ -91,7 +92,13 @@ def conv_rows(B, dev, reps=10, rotate_bytes=0, dtype="bf16", G=2, arch="resnet18
     return [_row(name, op, cnt, flops, nbytes, _time(fn, reps)) for name, op, cnt, flops, nbytes, fn in ops]
 
 
-def _make_f32(op, B, dev, C, H, W, K, R, st, pad, P, Q):
+def _make_f32(op, B, dev, C, H, W, K, R, st, pad, P, Q, terms=0):
+    return _f32_modes(op, B, dev, C, H, W, K, R, st, pad, P, Q, (terms,))[0]
+
+
+def _f32_modes(op, B, dev, C, H, W, K, R, st, pad, P, Q, modes):
+    """One callable per entry of `modes` (terms: 0 exact, 3 bf16x3, 6 bf16x6), all on the
+    same operand set."""
     from greedy_multimodal_learning_amd import conv as G
     from greedy_multimodal_learning_amd import _lib as L
     d = G._desc(B, H, W, C, K, R, R, st, pad)
@@ -100,12 +107,66 @@ def _make_f32(op, B, dev, C, H, W, K, R, st, pad, P, Q):
     dy = torch.randn(B, K, P, Q, device=dev).contiguous(memory_format=CL)
     if op == "fwd":
         y = torch.empty(B, K, P, Q, device=dev).contiguous(memory_format=CL)
-        return lambda: G.conv_f32(L.GM_CONV_FWD, d, x=x, w=w, out=y)
+        return [lambda t=t: G.conv_f32(L.GM_CONV_FWD, d, x=x, w=w, out=y, terms=t) for t in modes]
     if op == "dgrad":
         dx = torch.empty(B, C, H, W, device=dev).contiguous(memory_format=CL)
-        return lambda: G.conv_f32(L.GM_CONV_DGRAD, d, w=w, dy=dy, out=dx)
+        return [lambda t=t: G.conv_f32(L.GM_CONV_DGRAD, d, w=w, dy=dy, out=dx, terms=t) for t in modes]
     dw = torch.empty(K, C, R, R, device=dev).contiguous(memory_format=CL)
-    return lambda: G.conv_f32(L.GM_CONV_WGRAD, d, x=x, dy=dy, out=dw)
+    return [lambda t=t: G.conv_f32(L.GM_CONV_WGRAD, d, x=x, dy=dy, out=dw, terms=t) for t in modes]
+
+
+F32_MODES = (("exact", 0), ("bf16x3", 3), ("bf16x6", 6))
+
+
+def f32_mode_rows(B, dev, reps=5, rounds=5, rotate_bytes=320e6):
+    """The reference-precision table: every trunk convolution pass at batch B (one view) on
+    gm_conv2d_f32 (exact) and gm_conv2d_f32_split (bf16x3, bf16x6), the three modes timed
+    interleaved, `rounds` times each, on the same rotating operand sets.  Per row and mode:
+    median microseconds and the (max - min) / median spread over the rounds."""
+    import statistics
+    rows = []
+    for name, (C, H, W, K, R, st, pad, cnt) in TRUNK:
+        P, Q = (H + 2 * pad - R) // st + 1, (W + 2 * pad - R) // st + 1
+        flops = 2.0 * B * P * Q * K * C * R * R
+        xb, yb, wb = B * H * W * C * 4, B * P * Q * K * 4, K * C * R * R * 4
+        passes = ["fwd", "wgrad"] if C == 3 else ["fwd", "dgrad", "wgrad"]
+        for op in passes:
+            nbytes = xb + yb + wb
+            sets = max(1, -(-int(rotate_bytes) // nbytes)) if rotate_bytes else 1
+            per_set = [_f32_modes(op, B, dev, C, H, W, K, R, st, pad, P, Q, [t for _, t in F32_MODES])
+                       for _ in range(sets)]
+            fns = [_cycle([ps[i] for ps in per_set]) for i in range(len(F32_MODES))]
+            us = [[] for _ in F32_MODES]
+            for _ in range(rounds):
+                for i, fn in enumerate(fns):
+                    us[i].append(_time(fn, reps) * 1e6)
+            row = dict(name=name, op=op, count=cnt, flops=flops)
+            for (mode, _), v in zip(F32_MODES, us):
+                med = statistics.median(v)
+                row[mode] = med
+                row[mode + "_spread"] = (max(v) - min(v)) / med
+            rows.append(row)
+            del per_set, fns
+            torch.cuda.empty_cache()
+    return rows
+
+
+def markdown_f32(rows, B, reps, rounds):
+    out = [f"resnet18 fp32 trunk convolutions, one view, batch {B}: gm_conv2d_f32 (exact-f32 MFMA) against "
+           f"gm_conv2d_f32_split (bf16x3 / bf16x6), interleaved, median of {rounds} rounds of {reps} launches; "
+           f"spread = (max - min) / median over the rounds", "",
+           "| shape | pass | x/step | GFLOP | exact us (spread) | bf16x3 us (spread) | bf16x6 us (spread) | "
+           "exact/bf16x3 | exact/bf16x6 |", "|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        cells = " | ".join(f"{r[m]:.1f} ({r[m + '_spread'] * 100:.1f}%)" for m, _ in F32_MODES)
+        out.append(f"| {r['name']} | {r['op']} | {r['count']} | {r['flops'] / 1e9:.2f} | {cells} | "
+                   f"{r['exact'] / r['bf16x3']:.2f} | {r['exact'] / r['bf16x6']:.2f} |")
+    out.append("")
+    for m, _ in F32_MODES:
+        s = sum(r[m] * r["count"] for r in rows) * 1e-6
+        fl = sum(r["flops"] * r["count"] for r in rows)
+        out.append(f"conv family, {m}: {s * 1e3:.3f} ms per view = {fl / s / 1e12:.1f} TFLOP/s")
+    return "\n".join(out)
 
 
 def conv_ops_f32(B, dev, rotate_bytes=0):
@@ -352,10 +413,20 @@ def main():
                     help="trunk (resnet50: the C5 workload's, convolutions only; use --groups 1 --batch 32)")
     ap.add_argument("--rotate-mb", type=float, default=320.0,
                     help="conv launches rotate over operand sets of this many MB (0: one warm set)")
+    ap.add_argument("--f32", action="store_true",
+                    help="the reference-precision table: exact / bf16x3 / bf16x6 convolutions side by side")
+    ap.add_argument("--rounds", type=int, default=5, help="--f32: interleaved timing rounds per mode")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     from greedy_multimodal_learning_amd import build
     build.build()
+    if a.f32:
+        md = markdown_f32(f32_mode_rows(a.batch, dev, a.reps, a.rounds, a.rotate_mb * 1e6), a.batch, a.reps, a.rounds)
+        print(md)
+        if a.md:
+            with open(a.md, "w") as f:
+                f.write(md + "\n")
+        return
     rows = []
     if a.only in ("", "conv"):
         rows += conv_rows(a.batch, dev, a.reps, a.rotate_mb * 1e6, G=a.groups, arch=a.arch)
