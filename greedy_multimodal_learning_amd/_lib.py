@@ -393,3 +393,21 @@ EXPORTS.update({
     "gm_conv_set_stem": (c_int, [c_int]),
     "gm_conv_set_wgrad_stem": (c_int, [c_int]),
 })
+
+
+class BnCoefEntry(ctypes.Structure):
+    """gm_bn_coef_entry: one BatchNorm of gm_bn_infer_coef's device table (48 bytes)"""
+    _fields_ = [("gamma", c_void_p), ("beta", c_void_p), ("running_mean", c_void_p), ("running_var", c_void_p),
+                ("coef", c_void_p), ("C", c_int), ("eps", c_float)]
+
+
+# the evaluation pass: BatchNorm coefficients of a table, the convolution that applies them in its
+# epilogue, the metrics behind the heads
+EXPORTS.update({
+    "gm_bn_infer_coef": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "gm_conv2d_fwd_affine_ok": (c_int, [c_void_p, c_int]),
+    "gm_conv2d_fwd_grouped_affine_bf16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p,
+                                                  c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_size_t,
+                                                  c_void_p]),
+    "gm_eval_metrics": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+})

@@ -422,9 +422,11 @@ class MMTM_mitigate(nn.Module):
         return (yv, ys) + self._record(e_v, e_s, sq, visual.shape[1], return_scale, return_squeezed_mps)
 
     def forward_stacked(self, X, return_scale=False, return_squeezed_mps=False, turnoff_cross_modal_flow=False,
-                        average_squeezemaps=None, curation_mode=False, caring_modality=0):
+                        average_squeezemaps=None, curation_mode=False, caring_modality=0, on_device=False):
         """forward() on the view-batched trunk's stacked activation X = [visual; skeleton]
-        ([2B, C, H, W] channels_last, vtrunk.py): returns (Y stacked, scales, squeeze_array)."""
+        ([2B, C, H, W] channels_last, vtrunk.py): returns (Y stacked, scales, squeeze_array).
+        on_device: the recorded scales / squeezed maps stay device tensors (no host copy, so the
+        call can be captured in a graph: engine.EvalStep)."""
         if X.dtype not in ops._DT or X.shape[0] % 2 or not X.is_cuda:
             raise L.GreedyMMLError("MMTM stacked: fp32/bf16 HIP activations with an even batch")
         lay = ops.act_layout(X)
@@ -434,7 +436,7 @@ class MMTM_mitigate(nn.Module):
         cfg, prm = self._site(X.device, lay, return_squeezed_mps, turnoff_cross_modal_flow, average_squeezemaps,
                               curation_mode, caring_modality)
         Y, e_v, e_s, sq = _MMTMStackedFn.apply(X, *prm, cfg)
-        return (Y,) + self._record(e_v, e_s, sq, X.shape[1], return_scale, return_squeezed_mps)
+        return (Y,) + self._record(e_v, e_s, sq, X.shape[1], return_scale, return_squeezed_mps, on_device)
 
     def _site(self, dev, lay, return_squeezed_mps, turnoff_cross_modal_flow, average_squeezemaps, curation_mode,
               caring_modality):
@@ -475,13 +477,14 @@ class MMTM_mitigate(nn.Module):
             w_s, b_s = self._lin("fc_skeleton")
         return cfg, (w_sq, b_sq, w_sq_v, b_sq_v, w_sq_s, b_sq_s, w_v, b_v, w_s, b_s)
 
-    def _record(self, e_v, e_s, sq, C1, return_scale, return_squeezed_mps):
+    def _record(self, e_v, e_s, sq, C1, return_scale, return_squeezed_mps, on_device=False):
         self.step += 1
         self._step_mirror = self.step
-        scales = [e_v.cpu(), e_s.cpu()] if return_scale else None
+        host = (lambda t: t) if on_device else (lambda t: t.cpu())
+        scales = [host(e_v), host(e_s)] if return_scale else None
         squeeze_array = None
         if return_squeezed_mps:
-            squeeze_array = [sq[:, :C1].cpu(), sq[:, C1:].cpu()]
+            squeeze_array = [host(sq[:, :C1]), host(sq[:, C1:])]
         return scales, squeeze_array
 
 

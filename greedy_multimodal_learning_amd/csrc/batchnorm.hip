@@ -1564,6 +1564,19 @@ __global__ void k_bn_infer_coef(int C, const float* gamma, const float* beta, co
     coef[C + c] = (float)((double)beta[c] - (double)rm[c] * sc);
 }
 
+// The same coefficients for a table of BatchNorms in one launch (gm_bn_infer_coef): entry
+// blockIdx.y, the arithmetic of k_bn_infer_coef term for term, so the two agree bit for bit.
+__global__ void k_bn_infer_coef_table(const gm_bn_coef_entry* tab) {
+    const gm_bn_coef_entry e = tab[blockIdx.y];
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    const int C = e.C;
+    if (c >= C) return;
+    const double is = 1.0 / sqrt((double)e.running_var[c] + (double)e.eps);
+    const double sc = (double)e.gamma[c] * is;
+    e.coef[c] = (float)sc;
+    e.coef[C + c] = (float)((double)e.beta[c] - (double)e.running_mean[c] * sc);
+}
+
 inline int apply_grid(long long nvec, int C) {
     // ~4 vectors per thread, grid a multiple of nothing in particular: kT is a
     // multiple of C/8 so the channel group of a thread is fixed
@@ -2052,6 +2065,15 @@ extern "C" int gm_bn_bwd_bf16(const gm_bn_bwd* p, void* scratch, size_t bytes, v
 extern "C" int gm_bn_fwd_train_f32(const gm_bn_fwd* p, void* scratch, size_t bytes, void* stream) {
     return bn_fwd_train<float>(p, 1, false, scratch, bytes, stream, "gm_bn_fwd_train_f32");
 }
+extern "C" int gm_bn_infer_coef(const gm_bn_coef_entry* table, int n, int max_c, void* stream) {
+    const char* fn = "gm_bn_infer_coef";
+    GM_REQUIRE(table, "%s: null table", fn);
+    GM_REQUIRE(n >= 1 && n <= 65535, "%s: n must be 1..65535 (got %d)", fn, n);
+    GM_REQUIRE(max_c >= 1, "%s: max_c must be >= 1 (got %d)", fn, max_c);
+    hipLaunchKernelGGL(k_bn_infer_coef_table, dim3((max_c + 255) / 256, n), dim3(256), 0, as_stream(stream), table);
+    return check_launch("k_bn_infer_coef_table");
+}
+
 extern "C" int gm_bn_fwd_infer_f32(const gm_bn_fwd* p, void* scratch, size_t bytes, void* stream) {
     return bn_fwd_infer<float>(p, scratch, bytes, stream, "gm_bn_fwd_infer_f32");
 }

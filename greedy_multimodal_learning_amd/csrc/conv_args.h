@@ -78,6 +78,13 @@ struct ConvArgs {
     const float* bncoef;
     const float* bnmean;
     ConvCls cls[kMaxCls];
+    // forward, optional (the *_affine kernel forms alone read these; last, so the fields above keep
+    // their offsets): the evaluation epilogue y = act(acc sc[n] + sh[n] (+ addend)) with group g's
+    // fp32 [2][Nout] (sc, sh) at coef + g * gs_coef, the addend as the residual (no mask), act the
+    // NaN-propagating ReLU (relu != 0) or the identity; one rounding, no statistics
+    const float* coef;
+    long long gs_coef;
+    int relu;
 };
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));  // channel pairs: packed fp32 math
@@ -265,16 +272,43 @@ __device__ __forceinline__ void store_tile(const ConvArgs& a, const ConvCls& cl,
 // pixel row segment.  The direct 8-B stores from the MFMA layout touch 32 pixel rows per
 // instruction: 13 % of the layer-3 halo launch (41.4 us with, 36.0 without them).  Falls
 // back to store_tile when the LDS is too small or the output needs 64-bit offsets.
-template <int MT, int NT, int BM, int BN>
+// EPI = 1 (the *_affine kernels): acc sc[n] + sh[n] on the accumulators first, the ReLU after
+// the residual (a.addend) joined in fp32; the plan holds the LDS of the fp32 tile and 32-bit
+// output offsets (plan_epilogue), so there is no store_tile fallback and no statistics.
+template <int MT, int NT, int BM, int BN, int EPI = 0>
 __device__ __forceinline__ void store_tile_lds(const ConvArgs& a, const ConvCls& cl, int m0, int n0, int wm, int wn,
                                                int fr, int fh, int M, floatx16 (&acc)[MT][NT], long long goff,
                                                char* lds, int lds_bytes, int t, int grp) {
     static_assert(BM == 64 * MT && BN == 64 * NT, "store_tile_lds: 2 x 2 waves of MT x NT fragments");
     const size_t out_bytes = (size_t)a.N * a.Ho * a.Wo * a.Nout * 2;
     const bool f32 = a.addend != nullptr;
-    if (out_bytes >= 0x7ffff000u || BM * BN * (f32 ? 4 : 2) + 4 * (BN / 8) * 64 > lds_bytes) {
-        store_tile<MT, NT, BM, BN, true>(a, cl, m0, n0, wm, wn, fr, fh, M, acc, goff);
-        return;
+    if constexpr (EPI) {
+        const float* const cf = a.coef + (long long)grp * a.gs_coef;
+        const bool act = a.relu && !f32;  // with a residual the ReLU follows the join
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                int n = n0 + wn * (BN / 2) + j * 32 + 8 * gq + 4 * fh;  // this lane's 4 channels
+                n = n < a.Nout ? n : 0;                                  // (Nout % 8 == 0; not stored past it)
+                const float4 s = *reinterpret_cast<const float4*>(cf + n);
+                const float4 h = *reinterpret_cast<const float4*>(cf + a.Nout + n);
+#pragma unroll
+                for (int i = 0; i < MT; ++i) {
+                    float o0 = fmaf(acc[i][j][4 * gq], s.x, h.x), o1 = fmaf(acc[i][j][4 * gq + 1], s.y, h.y);
+                    float o2 = fmaf(acc[i][j][4 * gq + 2], s.z, h.z), o3 = fmaf(acc[i][j][4 * gq + 3], s.w, h.w);
+                    if (act) {
+                        o0 = relu_nan(o0); o1 = relu_nan(o1); o2 = relu_nan(o2); o3 = relu_nan(o3);
+                    }
+                    acc[i][j][4 * gq] = o0; acc[i][j][4 * gq + 1] = o1;
+                    acc[i][j][4 * gq + 2] = o2; acc[i][j][4 * gq + 3] = o3;
+                }
+            }
+    } else {
+        if (out_bytes >= 0x7ffff000u || BM * BN * (f32 ? 4 : 2) + 4 * (BN / 8) * 64 > lds_bytes) {
+            store_tile<MT, NT, BM, BN, true>(a, cl, m0, n0, wm, wn, fr, fh, M, acc, goff);
+            return;
+        }
     }
     constexpr int CH = BN / 8, CF = BN / 4;  // bf16 / fp32 16-B chunks per pixel row
     constexpr int NU = BM * CH / 256;          // output chunks per thread
@@ -358,6 +392,17 @@ __device__ __forceinline__ void store_tile_lds(const ConvArgs& a, const ConvCls&
             const int e = t + 256 * u, px = e / CH, c = e - px * CH;
             const float4 f0 = *reinterpret_cast<const float4*>(lds + px * (BN * 4) + (((2 * c) ^ (px & (CF - 1))) << 4));
             const float4 f1 = *reinterpret_cast<const float4*>(lds + px * (BN * 4) + (((2 * c + 1) ^ (px & (CF - 1))) << 4));
+            if constexpr (EPI) {
+                float z[8] = {f0.x + bf_lo(av[u].x), f0.y + bf_hi(av[u].x), f0.z + bf_lo(av[u].y), f0.w + bf_hi(av[u].y),
+                              f1.x + bf_lo(av[u].z), f1.y + bf_hi(av[u].z), f1.z + bf_lo(av[u].w), f1.w + bf_hi(av[u].w)};
+                if (a.relu) {
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) z[k] = relu_nan(z[k]);
+                }
+                const u32x4 o = {pack_bf2(z[0], z[1]), pack_bf2(z[2], z[3]), pack_bf2(z[4], z[5]), pack_bf2(z[6], z[7])};
+                __builtin_amdgcn_raw_buffer_store_b128(o, orsrc, off[u], 0, 0);
+                continue;
+            }
             const u32x4 o = {pack_bf2(f0.x + bf_lo(av[u].x), f0.y + bf_hi(av[u].x)),
                              pack_bf2(f0.z + bf_lo(av[u].y), f0.w + bf_hi(av[u].y)),
                              pack_bf2(f1.x + bf_lo(av[u].z), f1.y + bf_hi(av[u].z)),
@@ -374,6 +419,7 @@ __device__ __forceinline__ void store_tile_lds(const ConvArgs& a, const ConvCls&
     }
 #pragma unroll
     for (int u = 0; u < NU; ++u) __builtin_amdgcn_raw_buffer_store_b128(v[u], orsrc, off[u], 0, 0);
+    if constexpr (EPI) return;
     if (a.stats) {
         // BatchNorm statistics of the stored values (forward: y; input gradient: the BN
         // backward's dz against x): this thread's chunk c = t % CH (8 channels) over its NU

@@ -362,6 +362,67 @@ extern "C" int gm_conv2d_fwd_grouped_bf16(const gm_conv_desc_hw* d, int G, const
     return conv_fwd(d, G, true, x, w, w_stride, y, ws, ws_bytes, stream);
 }
 
+static void query_setup(const gm_conv_desc_hw* d, int G, ConvArgs& a);
+
+// does route_1x1 (with the stride-2 downsample, as the view-grouped forward routes) take d?
+static bool takes_1x1_fwd(const gm_conv_desc_hw* d) {
+    const long long M = (long long)d->N * d->H * d->W;
+    if (gm::conv1x1_ok(d->R, d->S, d->stride_h, d->stride_w, d->pad_h, d->pad_w, M, d->C, d->K)) return true;
+    const long long Mo = (long long)d->N * ((d->H - 1) / 2 + 1) * ((d->W - 1) / 2 + 1);
+    return gm::conv1x1s_ok(d->R, d->S, d->stride_h, d->stride_w, d->pad_h, d->pad_w, Mo, d->C, d->K) &&
+           M * d->C < (1ll << 30);
+}
+
+static const char* const kAffine1x1 =
+    "conv fwd affine: 1x1 shapes go to k_gemm_ring, which has no affine epilogue - run "
+    "gm_conv2d_fwd_grouped_bf16 and a coefficient-only gm_bn_fwd_apply_grouped_bf16";
+
+// The evaluation forward (include/greedymml.h): the view-grouped forward of
+// gm_conv2d_fwd_grouped_bf16 - the same plan under the same switches - with
+// y = act(acc sc[n] + sh[n] (+ residual)) as its epilogue.  1: the call below takes the shape.
+extern "C" int gm_conv2d_fwd_affine_ok(const gm_conv_desc_hw* d, int G) {
+    if (!d || check_desc_hw(d) || G < 1 || G > 64) return 0;
+    if (takes_1x1_fwd(d)) {
+        set_error("%s", kAffine1x1);
+        return 0;
+    }
+    ConvArgs a;
+    query_setup(d, G, a);
+    a.coef = reinterpret_cast<const float*>(16);
+    const ConvPlan p = plan_conv(a, 0, g_knobs);
+    if (p.rc != GM_OK) set_error("%s", p.err);
+    return p.rc == GM_OK;
+}
+
+extern "C" int gm_conv2d_fwd_grouped_affine_bf16(const gm_conv_desc_hw* d, int G, const void* x, const void* w,
+                                                 long long w_stride, void* y, const float* coef,
+                                                 long long coef_stride, const void* residual, int relu, void* ws,
+                                                 size_t ws_bytes, void* stream) {
+    const char* fn = "gm_conv2d_fwd_grouped_affine_bf16";
+    GM_REQUIRE(d, "%s: null descriptor d", fn);
+    int rc = check_desc_hw(d);
+    if (rc) return rc;
+    GM_REQUIRE(x && w && y, "%s: null x, w or y", fn);
+    GM_REQUIRE(coef && (reinterpret_cast<uintptr_t>(coef) & 15) == 0, "%s: coef null or not 16-byte aligned", fn);
+    GM_REQUIRE(coef_stride % 4 == 0 && (G == 1 || coef_stride >= 2ll * d->K || -coef_stride >= 2ll * d->K),
+               "%s: coef_stride %lld: a multiple of 4, at least 2 K floats apart", fn, coef_stride);
+    GM_REQUIRE((reinterpret_cast<uintptr_t>(y) & 15) == 0 && (reinterpret_cast<uintptr_t>(residual) & 15) == 0,
+               "%s: y and residual must be 16-byte aligned", fn);
+    if ((rc = check_groups(fn, G, w_stride, weight_elems(d)))) return rc;
+    if (takes_1x1_fwd(d)) {
+        set_error("%s", kAffine1x1);
+        return GM_E_UNSUP;
+    }
+    ConvArgs a;
+    fwd_setup(d, x, w, y, a);
+    set_groups(a, G, w_stride);
+    a.coef = coef;
+    a.gs_coef = coef_stride;
+    a.addend = static_cast<const uint16_t*>(residual);
+    a.relu = relu ? 1 : 0;
+    return pick_and_launch(a, as_stream(stream), ws, ws_bytes);
+}
+
 // an upper bound of the partial statistics rows any kernel takes for M output pixels, whatever the
 // switches say at the launch: 64-pixel tiles (k_gemm_ring, the lean kernel's smallest), k_conv_rw's
 // one row per workgroup

@@ -333,8 +333,10 @@ constexpr int kH9MaxQ = 12;  // halo DMA instructions per wave (nI <= 48)
 // LDS-DMA.  Measured and dropped (r03-r04): register-staged weights, a register prefetch of
 // the next chunk's halo, weight pieces spread between the k-slices' MFMAs (0.05-0.07 ms/step
 // slower or neutral).
-template <int BN, int NB>
-__global__ __launch_bounds__(256, 2) void k_conv_h9(ConvArgs a, HaloArgs h) {
+// (The kernel's text is conv_h9_body, inlined into k_conv_h9 - EPI = 0, the symbol and the code
+// of the training step - and into k_conv_h9_affine, EPI = 1: store_tile_lds's evaluation epilogue.)
+template <int BN, int NB, int EPI>
+__device__ __forceinline__ void conv_h9_body(const ConvArgs& a, const HaloArgs& h) {
     constexpr int BM = 128, MT = 2, NT = BN / 64, NW = 4;
     static_assert(NB >= 2 && NB <= 8, "ring depth");
     constexpr int BR = BN / (8 * NW);  // weight DMA instructions per wave per k-tile
@@ -619,7 +621,17 @@ __global__ __launch_bounds__(256, 2) void k_conv_h9(ConvArgs a, HaloArgs h) {
         }
         if (t == 0) __hip_atomic_store(a.flags + tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    store_tile_lds<MT, NT, 128, BN>(a, cl, m0, n0, wm, wn, fr, fh, M, acc, g * a.gs_out, lds, HB + NB * SB, t, g);
+    store_tile_lds<MT, NT, 128, BN, EPI>(a, cl, m0, n0, wm, wn, fr, fh, M, acc, g * a.gs_out, lds, HB + NB * SB, t, g);
+}
+
+template <int BN, int NB>
+__global__ __launch_bounds__(256, 2) void k_conv_h9(ConvArgs a, HaloArgs h) {
+    conv_h9_body<BN, NB, 0>(a, h);
+}
+
+template <int BN, int NB>
+__global__ __launch_bounds__(256, 2) void k_conv_h9_affine(ConvArgs a, HaloArgs h) {
+    conv_h9_body<BN, NB, 1>(a, h);
 }
 
 }  // namespace gm

@@ -188,13 +188,15 @@ __global__ __launch_bounds__(256) void k_conv_igemm(ConvArgs a) {
 // from LDS under the current k-step's MFMAs.  (PIPE: always 2 - it keeps the kernel's name in
 // the profiles; the __syncthreads form 0 and the 3-stage form 3 measured slower and are gone,
 // DESIGN.md section 8.)
-template <int BM, int BN, int PIPE = 2>
-__global__ __launch_bounds__(256) void k_conv_igemm_ut(ConvArgs a) {
+// (The kernel's text is conv_igemm_ut_body, inlined into k_conv_igemm_ut - EPI = 0, the symbol
+// and the code of the training step - and into k_conv_igemm_ut_affine, EPI = 1: the evaluation
+// epilogue of store_tile_lds, applied by the split that writes the output.)
+template <int BM, int BN, int EPI>
+__device__ __forceinline__ void conv_igemm_ut_body(const ConvArgs& a) {
     constexpr int BK = 64;
     constexpr int AR = BM / 32, BR = BN / 32;
     constexpr int MT = BM / 64, NT = BN / 64;
     constexpr int SA = BM * 128, SB = BN * 128;  // bytes per stage
-    static_assert(PIPE == 2, "k_conv_igemm_ut: one main-loop form");
     constexpr int NST = 2;                       // LDS stages
     extern __shared__ __attribute__((aligned(16))) uint4 smem[];
     char* lds = reinterpret_cast<char*>(smem);   // [A0..A(NST-1)][B0..B(NST-1)]
@@ -430,7 +432,19 @@ __global__ __launch_bounds__(256) void k_conv_igemm_ut(ConvArgs a) {
         if (t == 0) __hip_atomic_store(a.flags + tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 
-    store_tile_lds<MT, NT, BM, BN>(a, cl, m0, n0, wm, wn, fr, fh, M, acc, g * a.gs_out, lds, NST * (SA + SB), t, g);
+    store_tile_lds<MT, NT, BM, BN, EPI>(a, cl, m0, n0, wm, wn, fr, fh, M, acc, g * a.gs_out, lds, NST * (SA + SB), t,
+                                        g);
+}
+
+template <int BM, int BN, int PIPE = 2>
+__global__ __launch_bounds__(256) void k_conv_igemm_ut(ConvArgs a) {
+    static_assert(PIPE == 2, "k_conv_igemm_ut: one main-loop form");
+    conv_igemm_ut_body<BM, BN, 0>(a);
+}
+
+template <int BM, int BN>
+__global__ __launch_bounds__(256) void k_conv_igemm_ut_affine(ConvArgs a) {
+    conv_igemm_ut_body<BM, BN, 1>(a);
 }
 
 }  // namespace gm

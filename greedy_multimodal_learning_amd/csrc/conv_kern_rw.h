@@ -27,7 +27,10 @@ struct RwArgs {
 
 constexpr int kRwWeightBytes = 9 * 64 * 128;
 
-template <int Form = 0>  // one form (the template keeps the symbol of earlier profiles)
+// Form 0: the training step's kernel (the template keeps the symbol of earlier profiles).  Form 1,
+// the evaluation epilogue: acc sc[n] + sh[n] on the accumulators before they are packed (a.coef),
+// the residual through the addend path, the ReLU (a.relu) after the join; no statistics.
+template <int Form = 0>
 __global__ __launch_bounds__(256) void k_conv_rw(ConvArgs a, RwArgs r) {
     extern __shared__ __attribute__((aligned(16))) uint4 smem[];
     char* lds = reinterpret_cast<char*>(smem);  // [weights][halo 0][halo 1]
@@ -139,6 +142,16 @@ __global__ __launch_bounds__(256) void k_conv_rw(ConvArgs a, RwArgs r) {
     const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint16_t*>(a.bnx ? a.bnx + g * a.gs_out : cl.out), 0,
         (int)(out_bytes < 0x7fffffffu ? out_bytes : 0x7fffffffu), 0x00020000);
+    // Form 1: this lane's channels n = wn * 32 + 8 gq + 4 fh + 0..3, the same for every tile
+    float4 csc[Form == 1 ? 4 : 1], csh[Form == 1 ? 4 : 1];
+    if constexpr (Form == 1) {
+        const float* const cf = a.coef + (long long)g * a.gs_coef + wn * 32 + 4 * fh;
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+            csc[gq] = *reinterpret_cast<const float4*>(cf + 8 * gq);
+            csh[gq] = *reinterpret_cast<const float4*>(cf + 64 + 8 * gq);
+        }
+    }
     int bb = 0;
     for (; tl < r.tiles; tl += nwg) {
         const int nx = tl + nwg;
@@ -215,6 +228,20 @@ __global__ __launch_bounds__(256) void k_conv_rw(ConvArgs a, RwArgs r) {
             __builtin_amdgcn_sched_barrier(0);
         }
 
+        if constexpr (Form == 1) {
+            const bool act = a.relu && !a.addend;  // with a residual the ReLU follows the join
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    float o0 = fmaf(acc[i][4 * gq], csc[gq].x, csh[gq].x), o1 = fmaf(acc[i][4 * gq + 1], csc[gq].y, csh[gq].y);
+                    float o2 = fmaf(acc[i][4 * gq + 2], csc[gq].z, csh[gq].z), o3 = fmaf(acc[i][4 * gq + 3], csc[gq].w, csh[gq].w);
+                    if (act) {
+                        o0 = relu_nan(o0); o1 = relu_nan(o1); o2 = relu_nan(o2); o3 = relu_nan(o3);
+                    }
+                    acc[i][4 * gq] = o0; acc[i][4 * gq + 1] = o1; acc[i][4 * gq + 2] = o2; acc[i][4 * gq + 3] = o3;
+                }
+        }
         if (!a.addend) {
             // epilogue through LDS: the tile's RT whole image rows are one contiguous NHWC
             // block, assembled in LDS (16-B chunks XOR-swizzled by pixel) and written with
@@ -309,6 +336,11 @@ __global__ __launch_bounds__(256) void k_conv_rw(ConvArgs a, RwArgs r) {
                 if (a.addend) {
                     o0 += bf_lo(av[i][gq].x); o1 += bf_hi(av[i][gq].x);
                     o2 += bf_lo(av[i][gq].y); o3 += bf_hi(av[i][gq].y);
+                }
+                if constexpr (Form == 1) {
+                    if (a.relu) {
+                        o0 = relu_nan(o0); o1 = relu_nan(o1); o2 = relu_nan(o2); o3 = relu_nan(o3);
+                    }
                 }
                 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                 const u32x2 v = {pack_bf2(o0, o1), pack_bf2(o2, o3)};

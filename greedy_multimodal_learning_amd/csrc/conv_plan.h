@@ -66,6 +66,7 @@ struct ConvPlan {
     size_t ws_need = 0;              // split-K workspace that keeps every split the planner wants
     size_t ws_used = 0;              // ... and what this plan uses of the workspace it was given
     bool demask = false;             // the masked addend is materialised over dx first
+    bool affine = false;             // the *_affine form of the kernel (a.coef: the evaluation epilogue)
     int rc = GM_OK;                  // not GM_OK: no kernel serves the arguments (err says why)
     const char* err = nullptr;
     HaloArgs halo;
@@ -321,7 +322,7 @@ static void plan_halo_tiles(const ConvArgs& a, ConvPlan& p, int hb, bool groups)
 
 // The kernel for a: a pure function of a, the workspace bytes on offer (0 without a workspace),
 // the switches, the residency plan and the CU count.
-static ConvPlan plan_conv(const ConvArgs& a, size_t ws_bytes, const ConvKnobs& k) {
+static ConvPlan plan_kernel(const ConvArgs& a, size_t ws_bytes, const ConvKnobs& k) {
     ConvPlan p;
     TilePick t = pick_tile(a, k);
     const Halo256Plan h256 = halo256_plan(a, k);
@@ -404,6 +405,34 @@ static ConvPlan plan_conv(const ConvArgs& a, size_t ws_bytes, const ConvKnobs& k
     return p;
 }
 
+// The evaluation epilogue (a.coef) on the planned kernel: the kernels with an *_affine form keep
+// their plan - the LDS-staged ones with room for the fp32 tile, which their epilogue then takes
+// without a fallback - and the others decline (gm_conv2d_fwd_affine_ok).
+static void plan_epilogue(const ConvArgs& a, ConvPlan& p) {
+    if (p.rc != GM_OK) return;
+    p.affine = true;
+    if ((size_t)a.N * a.Ho * a.Wo * a.Nout * 2 >= 0x7ffff000u) {
+        p.rc = GM_E_UNSUP;
+        p.err = "conv affine: a group's output past 32-bit offsets";
+        return;
+    }
+    switch (p.kernel) {
+    case ConvKernel::rw: return;
+    case ConvKernel::h9:
+    case ConvKernel::lean: p.lds = std::max(p.lds, (size_t)p.BM * p.BN * 4); return;
+    default:
+        p.rc = GM_E_UNSUP;
+        p.err = "conv affine: the planned kernel (k_conv_halo, k_conv_igemm or k_conv_stem) has no affine "
+                "epilogue - run the plain forward and a coefficient-only BatchNorm apply";
+    }
+}
+
+static ConvPlan plan_conv(const ConvArgs& a, size_t ws_bytes, const ConvKnobs& k) {
+    ConvPlan p = plan_kernel(a, ws_bytes, k);
+    if (a.coef) plan_epilogue(a, p);
+    return p;
+}
+
 // one kernel instantiation: grow its dynamic LDS limit when this launch needs more, launch
 template <auto Kern, class... Extra>
 static int launch_form(const char* name, ConvArgs& a, const ConvPlan& p, hipStream_t st, const Extra&... extra) {
@@ -451,6 +480,30 @@ static int launch_conv(ConvArgs& a, const ConvPlan& p, void* ws, hipStream_t st)
         a.ws = reinterpret_cast<float*>(static_cast<char*>(ws) + kSplitkFlagBytes);
     }
     const int form = p.BM << 16 | p.BN << 8 | p.NB;
+    if (p.affine) {
+        switch (p.kernel) {
+        case ConvKernel::rw: return launch_form<k_conv_rw<1>>("k_conv_rw_affine", a, p, st, p.rw);
+        case ConvKernel::h9:
+            switch (form) {
+            case 128 << 16 | 128 << 8 | 2: return launch_form<k_conv_h9_affine<128, 2>>("k_conv_h9_affine", a, p, st, p.halo);
+            case 128 << 16 | 128 << 8 | 3: return launch_form<k_conv_h9_affine<128, 3>>("k_conv_h9_affine", a, p, st, p.halo);
+            case 128 << 16 | 64 << 8 | 3: return launch_form<k_conv_h9_affine<64, 3>>("k_conv_h9_affine", a, p, st, p.halo);
+            case 128 << 16 | 64 << 8 | 4: return launch_form<k_conv_h9_affine<64, 4>>("k_conv_h9_affine", a, p, st, p.halo);
+            case 128 << 16 | 64 << 8 | 5: return launch_form<k_conv_h9_affine<64, 5>>("k_conv_h9_affine", a, p, st, p.halo);
+            }
+            break;
+        case ConvKernel::lean:
+            switch (form) {
+            case 128 << 16 | 128 << 8: return launch_form<k_conv_igemm_ut_affine<128, 128>>("k_conv_igemm_affine", a, p, st);
+            case 128 << 16 | 64 << 8: return launch_form<k_conv_igemm_ut_affine<128, 64>>("k_conv_igemm_affine", a, p, st);
+            case 64 << 16 | 64 << 8: return launch_form<k_conv_igemm_ut_affine<64, 64>>("k_conv_igemm_affine", a, p, st);
+            }
+            break;
+        default: break;
+        }
+        set_error("conv affine: no compiled kernel for plan form %d x %d x %d", p.BM, p.BN, p.NB);
+        return GM_E_UNSUP;
+    }
     switch (p.kernel) {
     case ConvKernel::halo256: return launch_form<k_conv_halo<256, 128, 3>>("k_conv_halo", a, p, st, p.halo);
     case ConvKernel::rw: return launch_form<k_conv_rw<0>>("k_conv_rw", a, p, st, p.rw);

@@ -41,6 +41,9 @@ from .streams import alias_capture_stream, all_side_streams, capture_dropped, ca
     release_rng_capture_state, side_stream
 from .streams import enabled as streams_enabled
 from .vtrunk import drop_pending_wgrads
+from . import _lib as L
+from . import vtrunk
+from .head import head_ok, pooled_linear_stacked
 
 
 _DEBUG_BUCKETS = os.environ.get("GM_DEBUG_BUCKETS", "0") == "1"
@@ -708,3 +711,216 @@ class BalancedStep:
             if self.device_gate:  # push the unlock flag (int at byte offset 12)
                 flag = torch.tensor([int(bool(getattr(self.gate, "unlock", False)))], dtype=torch.int32)
                 self.gate_state[12:16].copy_(flag.view(torch.uint8))
+
+
+class EvalStep:
+    """One evaluation pass (train.evaluate's loop body) without a host sync per batch.
+
+        step = EvalStep(model)            # MMTM_MVCNN or MMTM_MVCNN_N
+        step.begin()                      # weights, BatchNorm coefficients, zeroed accumulators
+        for x, y in batches: outs, squeezed = step(x, y, curation)
+        loss, acc, acc_modal, n = step.result()   # the only sync; train.evaluate's units
+
+    bf16 (the default): the view-batched eval trunk (vtrunk.EvalTrunk - every BatchNorm's
+    running-statistics coefficients applied in its convolution's epilogue), the model's own MMTM
+    sites (forward_stacked with the model's mmtm_off / mmtm_rescale / saving_* flags and the
+    curation passed in; they advance their running averages and step exactly as the module path
+    does in eval mode: the same calls), the stacked heads and gm_eval_metrics, which adds the
+    batch's loss sum and correct counts to device accumulators.  The arithmetic is eval-mode
+    whatever the modules' training flag; no parameter or BatchNorm buffer is written.  With
+    graphs=True a batch shape's second appearance is captured as a hipGraph (keyed by the batch
+    shape, the curation setting and mmtm_off) and replayed from then on; a failed capture falls
+    back to eager batches for good.  The returned branch logits and squeezed maps are device
+    tensors - with graphs the graph's static outputs, valid until the next call.
+
+    compute_dtype=torch.float32: the module forward in eval mode (f32_contraction as set on the
+    model) under the same interface, with the device-side metrics; never captured."""
+
+    def __init__(self, model, compute_dtype=torch.bfloat16, graphs=True):
+        from .model import MMTM_MVCNN, MMTM_MVCNN_N
+        if not isinstance(model, (MMTM_MVCNN, MMTM_MVCNN_N)):
+            raise TypeError("EvalStep: MMTM_MVCNN or MMTM_MVCNN_N")
+        if compute_dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError("EvalStep: compute_dtype must be torch.bfloat16 or torch.float32")
+        self.model = model
+        self.compute_dtype = compute_dtype
+        self.fused = compute_dtype == torch.bfloat16
+        self.graphs = bool(graphs) and self.fused
+        self.two_view = isinstance(model, MMTM_MVCNN)
+        self.nviews = 2 if self.two_view else model.num_views
+        self.nets = [getattr(model, f"net_view_{i}") for i in range(self.nviews)]
+        self._mmtms = [getattr(model, f"mmtm{i}") for i in (2, 3, 4)]
+        self.device = next(model.parameters()).device
+        if self.device.type != "cuda":
+            raise L.GreedyMMLError("EvalStep: the model must be on a HIP device")
+        self.trunk = vtrunk.EvalTrunk(self.nets) if self.fused else None
+        self.acc = torch.zeros(3 + self.nviews, device=self.device, dtype=torch.int64)
+        self._graphs, self._static, self._seen = {}, {}, set()
+        self._gpool = None
+        self._sig = None
+        self.capture_failures = []
+        self.replays = 0
+
+    # ---- pass boundaries ----------------------------------------------------------------
+    def _signature(self):
+        """What a captured batch holds pointers to besides the trunk's own buffers."""
+        ps = [p.data_ptr() for n in self.nets for p in n.fc.parameters()]
+        for m in self._mmtms:
+            ps += [p.data_ptr() for p in m.parameters()]
+            ps.append(getattr(m, "_step_dev", None).data_ptr() if getattr(m, "_step_dev", None) is not None else 0)
+            ps.append(getattr(m, "_step_mirror", None) == m.step)
+            for name in ("running_avg_weight_visual", "running_avg_weight_skeleton"):
+                t = getattr(m, name, None)
+                ps.append(t.data_ptr() if torch.is_tensor(t) else 0)
+            ps += [t.data_ptr() for t in getattr(m, "running_avg", [])]
+            ps.append(getattr(m, "device_gate").data_ptr() if getattr(m, "device_gate", None) is not None else 0)
+        return tuple(ps)
+
+    def _drop_graphs(self):
+        if self._graphs:
+            torch.cuda.synchronize(self.device)  # no graph destroyed under a running replay
+        self._graphs, self._static, self._seen = {}, {}, set()
+        self._gpool = None
+
+    def begin(self):
+        """Start a pass: the bf16 weight copies and the BatchNorm coefficient table from the
+        model's current parameters and buffers; the accumulators zeroed."""
+        if self.fused:
+            self.trunk.refresh()
+        self.acc.zero_()
+
+    def result(self):
+        """(loss, acc, [acc_modal_i], n) of the pass so far, in train.evaluate's units: the
+        size-weighted mean of blend_loss, top-1 accuracies in percent.  One host sync."""
+        a = self.acc.cpu()
+        n = int(a[1])
+        d = max(n, 1)
+        return (float(a[:1].view(torch.float64)[0]) / d, 100.0 * int(a[2]) / d,
+                [100.0 * int(v) / d for v in a[3:]], n)
+
+    # ---- one batch ----------------------------------------------------------------------
+    def _forward(self, x, curation):
+        m = self.model
+        cm, caring = bool(curation[0]), curation[1]
+        if not self.fused:
+            was = m.training
+            m.eval()
+            try:
+                with torch.no_grad(), torch.autocast("cuda", enabled=False):
+                    _, outs, _, sq = m(x, curation_mode=cm, caring_modality=caring)
+            finally:
+                m.train(was)
+            return list(outs), sq
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):
+            tr = self.trunk
+            X = tr.layer(1, tr.stem(x))
+            squeezed = []
+            for i in (2, 3, 4):
+                X = tr.layer(i, X)
+                kw = dict(curation_mode=cm, caring_modality=caring, on_device=True)
+                if self.two_view:
+                    kw.update(turnoff_cross_modal_flow=bool(m.mmtm_off),
+                              average_squeezemaps=m.mmtm_rescale[i - 1] if m.mmtm_off else None)
+                elif caring is None:
+                    kw["caring_modality"] = 0
+                X, _, sq = getattr(m, f"mmtm{i}").forward_stacked(X, False, m.saving_mmtm_squeeze_array, **kw)
+                squeezed.append(sq)
+            fcs = [n.fc for n in self.nets]
+            B = X.shape[0] // self.nviews
+            fs = [X[i * B:(i + 1) * B] for i in range(self.nviews)]
+            if head_ok(fs, fcs) and all(isinstance(n.avgpool, torch.nn.AdaptiveAvgPool2d)
+                                        and n.avgpool.output_size in ((1, 1), 1) for n in self.nets):
+                outs = pooled_linear_stacked(X, fcs)
+            else:
+                outs = [n.fc(torch.flatten(n.avgpool(f), 1)) for n, f in zip(self.nets, fs)]
+        return list(outs), squeezed
+
+    def _batch(self, x, y, curation):
+        """Forward and metrics of one batch on the current stream; (outs, squeezed)."""
+        outs, squeezed = self._forward(x, curation)
+        outs = [o.float() for o in outs]
+        from .head import _joined
+        joined = _joined(outs)
+        if joined is None:
+            joined = torch.stack(outs)
+        nb, B, N = joined.shape
+        if y.dtype != torch.int64 or not y.is_cuda or y.shape != (B,):
+            raise ValueError("EvalStep: labels must be an int64 device tensor [B]")
+        L.check(L.load().gm_eval_metrics(joined.data_ptr(), nb, B, N, y.contiguous().data_ptr(), self.acc.data_ptr(),
+                                         L.stream_of(self.device)), "gm_eval_metrics")
+        rec = squeezed if getattr(self.model, "saving_mmtm_squeeze_array", False) else None
+        return outs, rec
+
+    def _graph_key(self, x, y, curation):
+        cm = bool(curation[0])
+        return (tuple(x.shape), tuple(x.stride()), x.dtype, cm, curation[1] if cm else None,
+                bool(getattr(self.model, "mmtm_off", False)),
+                bool(getattr(self.model, "saving_mmtm_squeeze_array", False)))
+
+    def _capture(self, key, curation):
+        steps = [(m, m.step) for m in self._mmtms]
+        g = torch.cuda.CUDAGraph()
+        if self._gpool is None:
+            self._gpool = torch.cuda.graph_pool_handle()
+        torch.cuda.synchronize(self.device)
+        eager_sid = torch.cuda.current_stream(self.device).stream_id
+        try:
+            with torch.cuda.graph(g, pool=self._gpool):
+                alias_capture_stream(self.device.index if self.device.index is not None
+                                     else torch.cuda.current_device(), eager_sid)
+                out = self._batch(*self._static[key], curation)
+        finally:
+            for m, st in steps:  # capture ran the Python forward but no kernel
+                m.step = st
+                m._step_mirror = st
+        self._graphs[key] = (g, out)
+        return self._graphs[key]
+
+    def __call__(self, x, y, curation=(False, None)):
+        """One batch (x [B, V, 3, H, W], y int64 [B], both on the device); returns the branch
+        logits (fp32 device tensors) and, when the model records them, the squeezed maps per
+        site (device tensors, the module path's nesting), else None.  No host sync."""
+        if not self.graphs:
+            return self._batch(x, y, curation)
+        sig = self._signature()
+        if sig != self._sig:  # parameters or MMTM state moved: captured pointers are stale
+            self._drop_graphs()
+            self._sig = sig
+        key = self._graph_key(x, y, curation)
+        if key not in self._seen:
+            # a shape's first batch runs eagerly: it grows every scratch buffer and sets the
+            # kernels' LDS limits outside a capture
+            self._seen.add(key)
+            out = self._batch(x, y, curation)
+            self._sig = self._signature()  # (the first site call makes its device step counter)
+            return out
+        entry = self._graphs.get(key)
+        if entry is None:
+            self._static[key] = (x.detach().clone(), y.detach().clone())
+            try:
+                entry = self._capture(key, curation)
+            except RuntimeError as e:  # capture refused on this system: eager from now on
+                self.capture_failures.append(str(e))
+                capture_dropped()  # (scratch grown in the failed capture was never zeroed)
+                try:
+                    release_rng_capture_state(self.device)
+                except RuntimeError as e2:
+                    self.capture_failures.append(f"release_rng_capture_state: {e2}")
+                import sys
+                print(f"[greedy_multimodal_learning_amd] EvalStep: hipGraph capture failed ({e}); eager batches "
+                      "from now on", file=sys.stderr, flush=True)
+                self.graphs = False
+                self._drop_graphs()
+                return self._batch(x, y, curation)
+        else:
+            sx, sy = self._static[key]
+            sx.copy_(x)
+            sy.copy_(y)
+        g, out = entry
+        g.replay()
+        capture_replayed()
+        self.replays += 1
+        for m in self._mmtms:
+            m.step += 1
+            m._step_mirror = m.step
+        return out

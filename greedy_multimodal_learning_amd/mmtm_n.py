@@ -290,9 +290,10 @@ class MMTM_N(nn.Module):
         return torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(dev)
 
     def forward_stacked(self, X, return_scale=False, return_squeezed_mps=False, turnoff_cross_modal_flow=False,
-                        average_squeezemaps=None, curation_mode=False, caring_modality=0):
+                        average_squeezemaps=None, curation_mode=False, caring_modality=0, on_device=False):
         """forward() over the view-batched trunk's stacked activation X = [x_0; ...; x_{N-1}]
-        ([N*B, C, H, W] channels_last, vtrunk.py): returns (Y stacked, scales, squeeze)."""
+        ([N*B, C, H, W] channels_last, vtrunk.py): returns (Y stacked, scales, squeeze).
+        on_device: the recorded scales / squeezed maps stay device tensors (engine.EvalStep)."""
         if X.shape[0] % self.N or not X.is_cuda or X.dtype not in ops._DT:
             raise L.GreedyMMLError("MMTM_N stacked: fp32/bf16 HIP activations with a batch divisible by N")
         lay = ops.act_layout(X)
@@ -303,7 +304,7 @@ class MMTM_N(nn.Module):
                                    curation_mode, caring_modality)
         outs = _MMTMNStackedFn.apply(cfg, self.fc_squeeze.weight, self.fc_squeeze.bias, X, *w_e, *b_e)
         return (outs[0],) + self._record(list(outs[1:1 + self.N]), outs[1 + self.N], return_scale,
-                                         return_squeezed_mps)
+                                         return_squeezed_mps, on_device)
 
     def _site(self, dev, lay, return_squeezed_mps, turnoff_cross_modal_flow, average_squeezemaps, curation_mode,
               caring_modality):
@@ -323,13 +324,14 @@ class MMTM_N(nn.Module):
                                     for a in average_squeezemaps]).contiguous()
         return cfg, [m.weight for m in self.fc_excite], [m.bias for m in self.fc_excite]
 
-    def _record(self, es, sq, return_scale, return_squeezed_mps):
+    def _record(self, es, sq, return_scale, return_squeezed_mps, on_device=False):
         self.step += 1
         self._step_mirror = self.step
-        scales = [e.cpu() for e in es] if return_scale else None
+        host = (lambda t: t) if on_device else (lambda t: t.cpu())
+        scales = [host(e) for e in es] if return_scale else None
         squeeze = None
         if return_squeezed_mps:
-            squeeze = [t.cpu() for t in torch.split(sq, self.dims, dim=1)]
+            squeeze = [host(t) for t in torch.split(sq, self.dims, dim=1)]
         return scales, squeeze
 
     def forward(self, xs, return_scale=False, return_squeezed_mps=False, turnoff_cross_modal_flow=False,

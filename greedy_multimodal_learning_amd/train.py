@@ -54,6 +54,17 @@ def f32_contraction_arg(compute_dtype, f32_contraction):
     return f32_contraction
 
 
+def eval_engine_arg(model, compute_dtype, eval_engine, graphs=True):
+    """The gin key `eval_engine` as evaluate()'s engine: None for "modules" (the module forward),
+    an engine.EvalStep over `model` (already on its device) for "fused"."""
+    if eval_engine == "modules":
+        return None
+    if eval_engine != "fused":
+        raise ValueError(f"eval_engine must be 'modules' or 'fused' (got {eval_engine!r})")
+    from .engine import EvalStep
+    return EvalStep(model, compute_dtype=compute_dtype, graphs=graphs)
+
+
 def construct_callbacks(names):
     """Reference train.py:53-57: instantiate (gin-bound) every named callback that the
     callbacks module provides (Bias_Mitigation_Strong / _Random, CompletedStopping,
@@ -71,13 +82,53 @@ def _metrics(lm, outs, y):
     return float(acc(lm, y)), [float(acc(o, y)) for o in outs]
 
 
-def evaluate(model, loader, phase, compute_dtype, steps=None, record_squeezed=False, curation=(False, None)):
+def _evaluate_fused(engine, loader, phase, steps, record_squeezed, curation):
+    """evaluate()'s loop on an engine.EvalStep: no host sync per batch - the loss sum and the
+    correct counts accumulate on the device (gm_eval_metrics), the recorded squeezed maps are
+    kept as device copies and brought to the host after the loop."""
+    idxs, squeezed = [], []
+    engine.begin()
+    for bi, (idx, x, y) in enumerate(loader):
+        if steps is not None and bi >= steps:
+            break
+        _, sq = engine(x, y, curation)
+        idxs.append(idx.numpy())
+        if record_squeezed:
+            if sq is None:
+                raise ValueError("record_squeezed needs model.saving_mmtm_squeeze_array")
+            # (device tensors may be a graph's static outputs, rewritten by the next batch)
+            squeezed.append([[v.detach().clone() if (torch.is_tensor(v) and v.is_cuda) else v for v in site]
+                             for site in sq if site is not None])
+    loss, a, am, n = engine.result()
+    out = {f"{phase}_loss": loss, f"{phase}_acc": a,
+           f"{phase}_indices": np.concatenate(idxs) if idxs else np.zeros(0, np.int64)}
+    if n:
+        for i, v in enumerate(am):
+            out[f"{phase}_acc_modal_{i}"] = np.float64(v)
+    if record_squeezed:
+        out[f"{phase}_squeezedmaps_array_list"] = [
+            [[v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v) for v in site] for site in b]
+            for b in squeezed]
+    return out
+
+
+def evaluate(model, loader, phase, compute_dtype, steps=None, record_squeezed=False, curation=(False, None),
+             engine=None):
     """Reference Model_._eval_generator (src/framework.py:216-248): eval mode, no grad,
     size-weighted loss and accuracies, the batches' indices, and (recording runs) the
     squeezed maps per batch (`{phase}_squeezedmaps_array_list`, :160-161).  `curation`:
     the (curation_mode, caring_modality) the model is called with, as Model_ passes its
-    own flags in evaluation too (src/framework.py:146-148)."""
+    own flags in evaluation too (src/framework.py:146-148).  `engine`: an engine.EvalStep
+    over `model` runs the batches instead of the module forward (the fused evaluation pass:
+    one host sync per pass); same keys and types."""
     model.eval()
+    if engine is not None:
+        if engine.model is not model:
+            raise ValueError("evaluate: the engine was built for another model")
+        try:
+            return _evaluate_fused(engine, loader, phase, steps, record_squeezed, curation)
+        finally:
+            model.train(True)
     n, loss_sum, acc_sum, accm_sum, idxs, squeezed = 0, 0.0, 0.0, None, [], []
     with torch.no_grad():
         for bi, (idx, x, y) in enumerate(loader):
@@ -124,7 +175,7 @@ def save_history(H, save_path, save_with_structure=True):
 def training_loop(model, loss_function, metrics, optimizer, config, save_path, steps_per_epoch, train=None,
                   valid=None, test=None, test_steps=None, validation_steps=None, use_gpu=True, device_numbers=[0],
                   custom_callbacks=[], checkpoint_monitor="val_acc", n_epochs=100, verbose=True, nummodalities=2,
-                  compute_dtype="fp32", graphs=True, f32_contraction="exact"):
+                  compute_dtype="fp32", graphs=True, f32_contraction="exact", eval_engine="modules"):
     """Reference src/training_loop.py:86-143 + Model_.train_loop (src/framework.py:
     250-330) on the fused engine.  `optimizer` is the (lr, momentum, wd) triple of the
     reference's SGD (only momentum = wd = 0, as every config uses, is fused; a torch SGD
@@ -136,7 +187,9 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
     `train_indices`), the validation / test dicts, and the gate's per-step lists; a NaN
     step loss or CompletedStopping ends training after that epoch (:321-322, :343);
     `model_best_val.pt` (best `checkpoint_monitor`) and `model_last_epoch.pt` (every
-    epoch) hold {'model', 'optimizer'} (src/training_loop.py:26-48, src/utils.py:107-115)."""
+    epoch) hold {'model', 'optimizer'} (src/training_loop.py:26-48, src/utils.py:107-115).
+    `eval_engine`: "modules" (the default: the module forward in eval mode) or "fused" (an
+    engine.EvalStep runs the validation / test passes)."""
     import math
 
     from .engine import BalancedStep
@@ -157,6 +210,7 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
     # the reference's optimizer object (never stepped: the engine's fused pass applies the
     # update with the learning rate read from it)
     opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=wd)
+    estep = eval_engine_arg(model, cdt, eval_engine, graphs)
     flags = step.flags  # the gate's model_pytoune; every other callback shares it
     flags.stop_training = False
     others = [c for c in custom_callbacks if c is not gate]
@@ -234,9 +288,9 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
             step.sync_gate()
         fl = (bool(step.flags.curation_mode), step.flags.caring_modality)
         if valid is not None:
-            logs.update(evaluate(model, valid, "val", cdt, validation_steps, curation=fl))
+            logs.update(evaluate(model, valid, "val", cdt, validation_steps, curation=fl, engine=estep))
         if test is not None:
-            logs.update(evaluate(model, test, "test", cdt, test_steps, curation=fl))
+            logs.update(evaluate(model, test, "test", cdt, test_steps, curation=fl, engine=estep))
         for k, v in logs.items():
             H.setdefault(k, []).append(v)
         # the reference's callback order: the custom callbacks (ReduceLROnPlateau_PyTorch,

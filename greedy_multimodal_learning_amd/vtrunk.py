@@ -834,3 +834,214 @@ def usable(model, nets, x):
                for m in mods):
             return False
     return True
+
+
+# ---- evaluation: BatchNorm with running statistics, folded into the convolutions ------------
+
+def vconv_affine(xb, G, wb, sb, K, R, S, stride, pad, area, residual=None, relu=True):
+    """y_g = act(conv(x_g, w_g) * sc_g + sh_g (+ residual_g)) per view group g of the stacked bf16
+    channels_last xb, rounded once (gm_conv2d_fwd_grouped_affine_bf16: the coefficients applied
+    to the fp32 accumulators in the convolution's epilogue).  wb: group 0's bf16 KRSC weight,
+    group g's sb elements on.  area: fp32 [G, 4K] with group g's (sc[K], sh[K]) in area[g, 2K:] -
+    the layout of gm_bn_fwd_apply_grouped_bf16's statistics buffer with one row, so the shapes
+    whose kernel has no such epilogue (gm_conv2d_fwd_affine_ok: the 1x1 convolutions on
+    k_gemm_ring) run the plain grouped forward and that apply, in place, with the same
+    coefficients."""
+    lib = L.load()
+    GN, C, H, W = xb.shape
+    N = GN // G
+    if GN != N * G or xb.dtype != BF or not xb.is_contiguous(memory_format=CL) or _cpad(C) != C:
+        raise L.GreedyMMLError(f"vconv_affine: stacked bf16 channels_last input of {G} groups (got {tuple(xb.shape)})")
+    if tuple(area.shape) != (G, 4 * K) or area.dtype != torch.float32 or not area.is_contiguous():
+        raise L.GreedyMMLError("vconv_affine: coefficient area must be fp32 [G, 4K]")
+    P, Q = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
+    dev = xb.device
+    y = torch.empty(GN, K, P, Q, device=dev, dtype=BF, memory_format=CL)
+    if residual is not None and (residual.shape != y.shape or residual.dtype != BF
+                                 or not residual.is_contiguous(memory_format=CL)):
+        raise L.GreedyMMLError("vconv_affine: the residual must be bf16 channels_last shaped like the output")
+    d = _desc_hw(N, H, W, C, K, R, S, stride, stride, pad, pad)
+    ws, nb = _splitk_g(dev, _desc(N, H, W, C, K, R, S, stride, pad), G, False)
+    st = L.stream_of(dev)
+    if lib.gm_conv2d_fwd_affine_ok(ctypes.byref(d), G) == 1:
+        L.check(lib.gm_conv2d_fwd_grouped_affine_bf16(ctypes.byref(d), G, xb.data_ptr(), wb.data_ptr(), sb,
+                                                      y.data_ptr(), area.data_ptr() + 8 * K, 4 * K, L.ptr(residual),
+                                                      int(bool(relu)), ws, nb, st),
+                "gm_conv2d_fwd_grouped_affine_bf16")
+        return y
+    if K % 64:
+        raise L.GreedyMMLError(f"vconv_affine: no kernel applies the coefficients for K = {K}")
+    L.check(lib.gm_conv2d_fwd_grouped_bf16(ctypes.byref(d), G, xb.data_ptr(), wb.data_ptr(), sb, y.data_ptr(), ws, nb,
+                                           st), "gm_conv2d_fwd_grouped_bf16")
+    # (the apply reads no parameter or statistic: their slots only have to be non-null)
+    a = area.data_ptr()
+    descs = [L.BnFwd(N * P * Q, K, int(bool(relu)), y[g * N:(g + 1) * N].data_ptr(),
+                     residual[g * N:(g + 1) * N].data_ptr() if residual is not None else 0,
+                     y[g * N:(g + 1) * N].data_ptr(), a, a, 0, 0, 0.0, 0.0, a, a, 0, 0, 0) for g in range(G)]
+    L.check(lib.gm_bn_fwd_apply_grouped_bf16(L.arr(L.BnFwd, descs), G, a, 1, st), "gm_bn_fwd_apply_grouped_bf16")
+    return y
+
+
+class _EvalPos:
+    """One convolution + BatchNorm position of every view: the modules, the views' bf16 KRSC
+    weights at one stride, the coefficient area."""
+
+    def __init__(self, convs, bns):
+        self.convs, self.bns = convs, bns
+        self.K, self.C, self.R, self.S = convs[0].weight.shape
+        self.stride, self.pad = convs[0].stride[0], convs[0].padding[0]
+        self.wb = self.area = None
+
+
+class EvalTrunk:
+    """The view-batched trunk in eval mode (model.eval(): every BatchNorm with its running
+    statistics), under torch.no_grad(), bf16 channels_last.  In eval mode a BatchNorm is
+    y = x*sc + sh with sc = gamma / sqrt(running_var + eps), sh = beta - running_mean*sc known
+    before its convolution starts, so each block is
+
+        conv1 with (sc, sh) and the ReLU in its epilogue,
+        the downsample convolution with (sc, sh),
+        conv2 (conv3 of a Bottleneck) with (sc, sh), the identity or downsample output as the
+        residual, and the ReLU,
+
+    one grouped launch each (vconv_affine), and the stem is the pixel-pair convolution followed by
+    gm_bn_relu_maxpool2d_fwd_grouped_bf16 with the running-statistics coefficients.  refresh()
+    makes the bf16 weight copies and every BatchNorm's coefficients (one gm_bn_infer_coef launch
+    over a table of all of them) from the modules' current parameters and buffers, which this
+    executor only reads (the stem's weight alone is packed from the module with every batch, in
+    the launch that packs the input).  No autograd state, ReLU mask bits or selected-x tensors are made; the
+    pool kernel's argmax bytes go to one scratch buffer kept here."""
+
+    def __init__(self, nets):
+        from .bn import GMBatchNorm2d
+        from .conv import GMConv2d
+        self.nets = list(nets)
+        self.G = G = len(self.nets)
+        if not 2 <= G <= 16:
+            raise L.GreedyMMLError("EvalTrunk: 2..16 views")
+        sig = None
+        for n in self.nets:
+            mods = [m for m in n.modules() if isinstance(m, (GMConv2d, GMBatchNorm2d))]
+            s = [(type(m).__name__, tuple(m.weight.shape)) for m in mods]
+            if sig is not None and s != sig:
+                raise L.GreedyMMLError("EvalTrunk: the views must share one architecture")
+            sig = s
+            if not n.conv1.uses_pair_stem() or any(
+                    isinstance(m, GMBatchNorm2d) and (not m.track_running_stats or not m.affine) for m in mods):
+                raise L.GreedyMMLError("EvalTrunk: pixel-pair stem, affine BatchNorms with running statistics")
+        n0 = self.nets[0]
+        self.stem_bns = [n.bn1 for n in self.nets]
+        self.blocks = {}  # layer index -> [dict(conv1=_EvalPos, conv2=..., conv3=..., ds=...)]
+        self.pos = []
+        for i in (1, 2, 3, 4):
+            layers = [getattr(n, f"layer{i}") for n in self.nets]
+            blks = []
+            for j in range(len(layers[0])):
+                bs = [lay[j] for lay in layers]
+                e = {}
+                for k in (1, 2, 3):
+                    if hasattr(bs[0], f"conv{k}"):
+                        e[f"conv{k}"] = _EvalPos([getattr(b, f"conv{k}") for b in bs], [getattr(b, f"bn{k}") for b in bs])
+                if bs[0].downsample is not None:
+                    e["ds"] = _EvalPos([b.downsample[0] for b in bs], [b.downsample[1] for b in bs])
+                for p in e.values():
+                    if not p.convs[0]._hip_ok() or _cpad(p.C) != p.C or p.K % 64:
+                        raise L.GreedyMMLError("EvalTrunk: only the ResNet trunk's convolutions")
+                self.pos.extend(e.values())
+                blks.append(e)
+            self.blocks[i] = blks
+        from .pool import _pair1
+        self.pool = tuple(_pair1(getattr(n0.maxpool, a)) for a in ("kernel_size", "stride", "padding"))
+        self.coef = self.stem_coef = self._table = self._idx = None
+        self._n_entries = self._max_c = 0
+
+    def refresh(self):
+        """bf16 weights and BatchNorm coefficients from the modules as they are now."""
+        lib = L.load()
+        G = self.G
+        dev = self.nets[0].conv1.weight.device
+        st = L.stream_of(dev)
+        if self.coef is None or self.coef.device != dev:
+            Cs = self.stem_bns[0].weight.shape[0]
+            total = G * 2 * Cs + sum(G * 4 * p.K for p in self.pos)
+            self.coef = torch.zeros(total, device=dev, dtype=torch.float32)
+            self.stem_coef = self.coef[:G * 2 * Cs].view(G, 2 * Cs)
+            off = G * 2 * Cs
+            for p in self.pos:
+                p.area = self.coef[off:off + G * 4 * p.K].view(G, 4 * p.K)
+                off += G * 4 * p.K
+                p.wb = torch.empty(G, p.K, p.R, p.S, p.C, device=dev, dtype=BF)
+        ents = []
+
+        def entry(bn, out_ptr):
+            if bn.running_mean is None or bn.running_mean.dtype != torch.float32 or bn.weight.dtype != torch.float32:
+                raise L.GreedyMMLError("EvalTrunk: fp32 BatchNorm parameters and running statistics")
+            ents.append(L.BnCoefEntry(bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                                      bn.running_var.data_ptr(), out_ptr, bn.weight.shape[0], float(bn.eps)))
+        for g, bn in enumerate(self.stem_bns):
+            entry(bn, self.stem_coef[g].data_ptr())
+        for p in self.pos:
+            for g, bn in enumerate(p.bns):
+                entry(bn, p.area[g].data_ptr() + 8 * p.K)
+        raw = bytes(L.arr(L.BnCoefEntry, ents))
+        if self._table is None or self._table.device != dev or self._table.numel() != len(raw):
+            self._table = torch.empty(len(raw), device=dev, dtype=torch.uint8)
+        self._table.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+        L.check(lib.gm_bn_infer_coef(self._table.data_ptr(), len(ents), max(e.C for e in ents), st),
+                "gm_bn_infer_coef")
+        for p in self.pos:
+            for g, c in enumerate(p.convs):
+                w32 = _nhwc(c.weight.detach().float())
+                L.check(lib.gm_conv_weight_prep_bf16(w32.data_ptr(), p.K, p.R * p.S, p.C, p.C, p.wb[g].data_ptr(), 0,
+                                                     st), "gm_conv_weight_prep_bf16")
+
+    def stem(self, x):
+        """layer-1 input of every view, stacked: maxpool(relu(bn1(conv1(x[:, g])))) per net g."""
+        lib = L.load()
+        G = self.G
+        nets = self.nets
+        B, _, C0, H, W = x.shape
+        K, _, R, S = nets[0].conv1.weight.shape
+        pad = nets[0].conv1.padding[0]
+        P, Q, Sp, Hp, Wp = _stem_geom(H, W, R, S, pad)
+        dev = x.device
+        st = L.stream_of(dev)
+        xp = torch.empty(G * B, Hp, Wp // 2, 8, device=dev, dtype=BF)
+        wp = torch.empty(G, K, R, Sp, 8, device=dev, dtype=BF)
+        weights = [n.conv1.weight.detach() for n in nets]
+        if G <= 4:
+            stem_pack_grouped([x[:, g] for g in range(G)], weights, pad, xp, wp)
+        else:
+            for g in range(G):
+                stem_pack(x[:, g], weights[g], pad, xp=xp[g * B:(g + 1) * B], wp=wp[g])
+        y = torch.empty(G * B, K, P, Q, device=dev, dtype=BF, memory_format=CL)
+        d = _desc_hw(B, Hp, Wp // 2, 8, K, R, Sp, 2, 1, 0, 0)
+        L.check(lib.gm_conv2d_fwd_grouped_bf16(ctypes.byref(d), G, xp.data_ptr(), wp.data_ptr(), K * R * Sp * 8,
+                                               y.data_ptr(), 0, 0, st), "gm_conv2d_fwd_grouped_bf16")
+        k, s, p = self.pool
+        Pp, Qp = (P + 2 * p - k) // s + 1, (Q + 2 * p - k) // s + 1
+        out = torch.empty(G * B, K, Pp, Qp, device=dev, dtype=BF, memory_format=CL)
+        if self._idx is None or self._idx.numel() < out.numel() or self._idx.device != dev:
+            self._idx = torch.empty(out.numel(), device=dev, dtype=torch.uint8)
+        pd = L.PoolDesc(B, P, Q, K, k, s, p)
+        L.check(lib.gm_bn_relu_maxpool2d_fwd_grouped_bf16(ctypes.byref(pd), G, y.data_ptr(), self.stem_coef.data_ptr(),
+                                                          out.data_ptr(), self._idx.data_ptr(), 0, st),
+                "gm_bn_relu_maxpool2d_fwd_grouped_bf16")
+        return out
+
+    def _cbn(self, X, p, residual=None, relu=True):
+        return vconv_affine(X, self.G, p.wb[0], p.K * p.R * p.S * p.C, p.K, p.R, p.S, p.stride, p.pad, p.area,
+                            residual, relu)
+
+    def layer(self, i, X):
+        """layer{i} of every view over the stacked X (BasicBlock.forward / Bottleneck.forward)."""
+        X = _nhwc(X)
+        for e in self.blocks[i]:
+            idt = self._cbn(X, e["ds"], relu=False) if "ds" in e else X
+            out = self._cbn(X, e["conv1"])
+            if "conv3" in e:
+                out = self._cbn(out, e["conv2"])
+                X = self._cbn(out, e["conv3"], residual=idt)
+            else:
+                X = self._cbn(out, e["conv2"], residual=idt)
+        return X

@@ -772,6 +772,58 @@ typedef struct gm_views_norm {
 
 int gm_views_normalize(const gm_views_norm* p, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * The evaluation pass (model.eval(): BatchNorm with its running statistics).  In eval mode a
+ * BatchNorm's y = x*sc + sh has sc = gamma / sqrt(running_var + eps), sh = beta -
+ * running_mean*sc before its convolution starts, so the convolution applies it in its epilogue
+ * and the activation crosses HBM once instead of three times.
+ *
+ * gm_bn_infer_coef: the coefficients of a table of BatchNorms in ONE launch.  table: n entries
+ * in DEVICE memory (the pointers in them device pointers too), max_c >= every entry's C.  Entry
+ * i's coef receives fp32 [2][C] (sc, then sh), by gm_bn_fwd_infer_*'s own arithmetic: the two
+ * agree bit for bit.  The host checks table, n and max_c; the entries are the caller's.
+ *
+ * gm_conv2d_fwd_grouped_affine_bf16: gm_conv2d_fwd_grouped_bf16 (same plan, same switches, same
+ * workspace) with the epilogue
+ *     y = act(acc * sc[n] + sh[n] (+ residual))
+ * acc the fp32 accumulator, group g's coefficients fp32 [2][K] at coef + g*coef_stride (floats;
+ * 16-byte aligned, coef_stride a multiple of 4), residual optional bf16 in y's layout and
+ * stacking (may be y itself), act the NaN-propagating ReLU (relu != 0) or the identity; one
+ * rounding to bf16, no statistics.  Taken by k_conv_rw, k_conv_h9 and k_conv_igemm_ut (split-K
+ * included: the last split applies it).  GM_E_UNSUP, nothing launched and gm_last_error saying
+ * why, for the shapes the plan gives to k_gemm_ring (1x1), k_conv_halo, k_conv_igemm (C < 64),
+ * k_conv_stem, or outputs past 32-bit offsets: there run gm_conv2d_fwd_grouped_bf16, then
+ * gm_bn_fwd_apply_grouped_bf16 with rows = 1 over a coefficient area laid out as its statistics
+ * buffer (group g's [2][K] at stats + g*4K + 2K).  gm_conv2d_fwd_affine_ok: 1 when the call takes
+ * the shape under the current switches, else 0.
+ *
+ * gm_eval_metrics: one launch behind the heads.  logits fp32 [nbranch][B][N] (nbranch <= 8),
+ * labels int64 [B]; acc: 3 + nbranch 8-byte words the caller owns and zeroes, ADDED to:
+ *   [0] double  sum over samples and branches of the cross-entropy (blend_loss * B)
+ *   [1] int64   samples
+ *   [2] int64   correct top-1 of the branch-mean logits (the fp32 mean as losses.acc takes it)
+ *   [3 + i]     int64 correct top-1 of branch i
+ * The first maximal index wins a tie.  A label outside [0, N) makes [0] NaN (as gm_xent_fwd)
+ * and is never correct.  One workgroup, fixed reduction order, no atomics: deterministic.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+    const float* gamma;
+    const float* beta;
+    const float* running_mean;
+    const float* running_var;
+    float* coef;              /* out: [2][C] */
+    int C;
+    float eps;
+} gm_bn_coef_entry;
+
+int gm_bn_infer_coef(const gm_bn_coef_entry* table, int n, int max_c, void* stream);
+int gm_conv2d_fwd_affine_ok(const gm_conv_desc_hw* d, int G);
+int gm_conv2d_fwd_grouped_affine_bf16(const gm_conv_desc_hw* d, int G, const void* x, const void* w,
+                                      long long w_stride, void* y, const float* coef, long long coef_stride,
+                                      const void* residual, int relu, void* ws, size_t ws_bytes, void* stream);
+int gm_eval_metrics(const float* logits, int nbranch, int B, int N, const long long* labels, void* acc,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,107 @@
+"""gm_eval_metrics: the evaluation pass's loss sum and correct counts in one launch, added to
+device accumulators - against losses.blend_loss / losses.acc on the same tensors.
+
+Counts are integers and must be equal.  The loss sum is a sum of fp32 per-row terms (lse in
+fp32, as gm_xent_fwd) accumulated in fp64; against blend_loss * B recomputed in fp64 the per-row
+fp32 rounding (2^-24 relative on terms of size ~ log N + |logit|) leaves well under rtol 1e-5."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+N = 40
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    return torch.device("cuda:0")
+
+
+def _metrics(logits, y, acc=None):
+    """logits [nbranch][B][N] fp32 on the device; returns the accumulator (int64 [3 + nbranch])."""
+    from greedy_multimodal_learning_amd import _lib as L
+    nb, B, n = logits.shape
+    if acc is None:
+        acc = torch.zeros(3 + nb, device=logits.device, dtype=torch.int64)
+    L.check(L.load().gm_eval_metrics(logits.data_ptr(), nb, B, n, y.data_ptr(), acc.data_ptr(),
+                                     L.stream_of(logits.device)), "gm_eval_metrics")
+    return acc
+
+
+def _read(acc):
+    a = acc.cpu()
+    return float(a[:1].view(torch.float64)[0]), int(a[1]), int(a[2]), [int(v) for v in a[3:]]
+
+
+def _want(logits, y):
+    from greedy_multimodal_learning_amd.losses import acc as top1
+    outs = [logits[i] for i in range(logits.shape[0])]
+    B = logits.shape[1]
+    loss = sum(F.cross_entropy(o.double(), y, reduction="sum") for o in outs)
+    hits = lambda a: int(round(float(a) * B / 100))
+    return float(loss), B, hits(top1(outs, y)), [hits(top1(o, y)) for o in outs]
+
+
+@pytest.mark.parametrize("nb", [2, 4])
+@pytest.mark.parametrize("B", [1, 3, 64])
+def test_counts_equal_and_loss_close(dev, nb, B):
+    g = torch.Generator().manual_seed(100 * nb + B)
+    logits = (3 * torch.randn(nb, B, N, generator=g)).to(dev)
+    y = torch.randint(0, N, (B,), generator=g).to(dev)
+    # make some predictions right, so the counts are not all zero
+    for b in range(0, B, 2):
+        logits[b % nb, b, y[b]] += 12.0
+    loss, n, hit, hits = _read(_metrics(logits, y))
+    wl, wn, wh, whs = _want(logits, y)
+    print(f"nb {nb} B {B}: loss {loss!r} vs {wl!r} (rel {abs(loss - wl) / abs(wl):.3g}); counts {hit} {hits}")
+    assert (n, hit, hits) == (wn, wh, whs)
+    assert sum(hits) > 0
+    assert abs(loss - wl) <= 1e-5 * abs(wl)
+
+
+def test_two_calls_accumulate(dev):
+    g = torch.Generator().manual_seed(7)
+    a = (2 * torch.randn(2, 5, N, generator=g)).to(dev)
+    b = (2 * torch.randn(2, 3, N, generator=g)).to(dev)
+    ya, yb = torch.randint(0, N, (5,), generator=g).to(dev), torch.randint(0, N, (3,), generator=g).to(dev)
+    a[0, 1, ya[1]] += 20.0
+    b[:, 2, yb[2]] += 20.0
+    acc = _metrics(a, ya)
+    one = _read(acc)
+    _metrics(b, yb, acc)
+    loss, n, hit, hits = _read(acc)
+    wa, wb = _want(a, ya), _want(b, yb)
+    assert n == 8 and one[1] == 5
+    assert hit == wa[2] + wb[2] and hits == [p + q for p, q in zip(wa[3], wb[3])]
+    assert abs(loss - (wa[0] + wb[0])) <= 1e-5 * abs(wa[0] + wb[0])
+    # deterministic: the same two calls again give the same bits
+    acc2 = _metrics(b, yb, _metrics(a, ya))
+    assert torch.equal(acc, acc2)
+
+
+def test_tie_picks_the_first_index(dev):
+    logits = torch.zeros(2, 3, N, device=dev)
+    # sample 0: indices 5 and 9 tie in both branches and in the mean; sample 1: branch 0 has its
+    # maximum at 7, branch 1 at 3, and the mean ties between them (first: 3); sample 2: all equal (0)
+    logits[:, 0, 5] = logits[:, 0, 9] = 2.0
+    logits[0, 1, 7] = logits[1, 1, 3] = 4.0
+    for y, want in (([5, 3, 0], (3, [2, 3])),([9, 7, 1], (0, [1, 0]))):
+        yt = torch.tensor(y, device=dev)
+        _, n, hit, hits = _read(_metrics(logits, yt))
+        assert (n, hit, hits) == (3, want[0], want[1]), y
+        w = _want(logits, yt)
+        assert (hit, hits) == (w[2], w[3])  # torch.argmax breaks ties the same way
+
+
+def test_label_out_of_range(dev):
+    g = torch.Generator().manual_seed(11)
+    logits = torch.randn(2, 4, N, generator=g).to(dev)
+    y = torch.tensor([1, N, -1, 2], device=dev)
+    logits[:, 0, 1] += 20.0
+    logits[:, 3, 2] += 20.0
+    loss, n, hit, hits = _read(_metrics(logits, y))
+    assert loss != loss  # NaN, as gm_xent_fwd
+    assert (n, hit, hits) == (4, 2, [2, 2])
