@@ -308,6 +308,7 @@ EXPORTS.update({
     "gm_conv2d_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "gm_conv2d_f32_split_scratch": (c_size_t, [c_void_p, c_int]),
     "gm_conv2d_f32_split": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "gm_conv2d_f32_affine": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "gm_bn_fwd_train_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "gm_bn_fwd_infer_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "gm_bn_bwd_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),

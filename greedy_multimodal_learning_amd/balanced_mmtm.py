@@ -406,7 +406,9 @@ class MMTM_mitigate(nn.Module):
 
     def forward(self, visual, skeleton, return_scale=False, return_squeezed_mps=False,
                 turnoff_cross_modal_flow=False, average_squeezemaps=None, curation_mode=False,
-                caring_modality=0):
+                caring_modality=0, on_device=False):
+        """on_device: the recorded scales / squeezed maps stay device tensors (no host copy, so the
+        call can be captured in a graph: engine.EvalStep's fp32 form)."""
         ops._dev_check(visual, skeleton)
         if visual.dtype not in ops._DT or skeleton.dtype != visual.dtype:
             raise L.GreedyMMLError(f"MMTM activations must be fp32 or bf16 (got {visual.dtype}, "
@@ -419,7 +421,7 @@ class MMTM_mitigate(nn.Module):
         cfg, prm = self._site(visual.device, lay, return_squeezed_mps, turnoff_cross_modal_flow, average_squeezemaps,
                               curation_mode, caring_modality)
         yv, ys, e_v, e_s, sq = _MMTMFunction.apply(visual, skeleton, *prm, cfg)
-        return (yv, ys) + self._record(e_v, e_s, sq, visual.shape[1], return_scale, return_squeezed_mps)
+        return (yv, ys) + self._record(e_v, e_s, sq, visual.shape[1], return_scale, return_squeezed_mps, on_device)
 
     def forward_stacked(self, X, return_scale=False, return_squeezed_mps=False, turnoff_cross_modal_flow=False,
                         average_squeezemaps=None, curation_mode=False, caring_modality=0, on_device=False):

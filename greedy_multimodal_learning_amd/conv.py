@@ -492,6 +492,24 @@ def conv_f32(mode, d, x=None, w=None, dy=None, out=None, addend=None, accumulate
     return out
 
 
+def conv_f32_affine(d, x, w, out, coef, residual=None, relu=False, terms=0):
+    """One gm_conv2d_f32_affine call: the fp32 forward convolution (channels_last x, KRSC w, `out`
+    preallocated NHWC) with an eval-mode BatchNorm in its epilogue - coef fp32 [2][K] (sc then sh,
+    gm_bn_infer_coef's layout), the optional residual (out's layout; may be `out`) and ReLU.  The
+    result equals conv_f32(FWD, terms) followed by bn.bn_fwd_infer bit for bit.  terms as conv_f32;
+    the library refuses any other value (GreedyMMLError) before it launches anything."""
+    terms = int(terms)
+    lib = L.load()
+    p = L.ConvF32(L.GM_CONV_FWD, d, L.ptr(x), L.ptr(w), 0, L.ptr(out), 0, 0, 0)
+    dev = out.device
+    need = lib.gm_conv2d_f32_scratch(ctypes.byref(p)) if terms == 0 else \
+        lib.gm_conv2d_f32_split_scratch(ctypes.byref(p), terms)
+    scratch = torch.empty(max(need, 16), device=dev, dtype=torch.uint8) if need else None
+    L.check(lib.gm_conv2d_f32_affine(ctypes.byref(p), terms, L.ptr(coef), L.ptr(residual), int(bool(relu)),
+                                     L.ptr(scratch), need, L.stream_of(dev)), "gm_conv2d_f32_affine")
+    return out
+
+
 def _f32_cl(t):
     t = t if t.dtype == torch.float32 else t.float()
     return _nhwc(t)

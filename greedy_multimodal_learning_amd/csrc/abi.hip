@@ -52,6 +52,27 @@ extern "C" int gm_device_faults(unsigned* out, int clear) {
     return GM_OK;
 }
 
+// The fp32 forward convolution with the eval-mode BatchNorm in its epilogue: every argument
+// is checked here, before a plan is made or anything is launched.
+extern "C" int gm_conv2d_f32_affine(const gm_conv_f32* p, int terms, const float* coef, const float* residual,
+                                    int relu, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* fn = "gm_conv2d_f32_affine";
+    GM_REQUIRE(p, "%s: null descriptor", fn);
+    GM_REQUIRE(p->mode == GM_CONV_FWD, "%s: mode must be GM_CONV_FWD (got %d)", fn, p->mode);
+    GM_REQUIRE(!p->accumulate, "%s: accumulate must be 0", fn);
+    GM_REQUIRE(!p->addend, "%s: addend must be NULL (a dgrad option)", fn);
+    GM_REQUIRE(terms == 0 || terms == 3 || terms == 6,
+               "%s: terms must be 0 (exact), 3 (bf16x3) or 6 (bf16x6), got %d", fn, terms);
+    GM_REQUIRE(coef, "%s: null coef", fn);
+    GM_REQUIRE(reinterpret_cast<uintptr_t>(coef) % 4 == 0, "%s: coef must be 4-byte aligned", fn);
+    GM_REQUIRE(reinterpret_cast<uintptr_t>(residual) % 4 == 0, "%s: residual must be 4-byte aligned", fn);
+    GM_REQUIRE(p->out, "%s: null out", fn);
+    GM_REQUIRE(p->x, "%s: null x", fn);
+    GM_REQUIRE(p->w, "%s: null w", fn);
+    if (terms == 0) return gm::conv_f32_affine_exact(p, coef, residual, relu, scratch, scratch_bytes, stream);
+    return gm::conv_f32_affine_split(p, terms, coef, residual, relu, scratch, scratch_bytes, stream);
+}
+
 extern "C" int gm_set_spin_limit(unsigned polls) {
     gm::g_spin_limit = polls;
     return GM_OK;

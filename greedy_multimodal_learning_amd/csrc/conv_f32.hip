@@ -24,8 +24,10 @@ constexpr int kPad = 32;  // row stride = 64*T + 32 == 32 (mod 64) dwords
 
 // ---- the kernel ------------------------------------------------------------------
 // VEC: 16-byte operand loads (C % 4 == 0 and K % 4 == 0), else element loads.
-template <int MODE, bool VEC, int TM, int TN>
+// AFF (FWD only): the affine epilogue of gm_conv2d_f32_affine (affine_epilogue, conv_f32_common.h).
+template <int MODE, bool VEC, int TM, int TN, bool AFF = false>
 __global__ __launch_bounds__(256) void k_conv_f32(F32Args a) {
+    static_assert(!AFF || MODE == FWD, "the affine epilogue is a forward form");
     constexpr int BM = 64 * TM, BN = 64 * TN;
     constexpr int LA = BM + kPad, LB = BN + kPad;
     __shared__ float As[2][kBK][LA];
@@ -219,13 +221,20 @@ __global__ __launch_bounds__(256) void k_conv_f32(F32Args a) {
         for (int j = 0; j < TN; ++j) {
             const int n = n0 + wn * 32 * TN + j * 32 + li;
             if (n >= a.N) continue;
+            float sc = 0.f, sh = 0.f;  // AFF: the lane's column coefficients, once per 32-column block
+            if (AFF && !split) {
+                sc = a.coef[n];
+                sh = a.coef[a.N + n];
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
                 if (m >= a.M) continue;
                 const size_t o = (size_t)m * a.N + n;
                 float v = acc[i][j][r];
-                if (!split) {
+                if (AFF) {  // (split: the sum kernel applies it)
+                    if (!split) v = affine_epilogue(v, sc, sh, a.residual, o, a.relu);
+                } else if (!split) {
                     if (a.addend) v += a.addend[o];
                     if (a.accumulate) v += dst[o];
                 }
@@ -245,7 +254,31 @@ void launch(const Plan& pl, hipStream_t st) {
 #undef GM_F32_L
 }
 
+void launch_affine(const Plan& pl, hipStream_t st) {
+#define GM_F32_L(V, TM, TN) hipLaunchKernelGGL((k_conv_f32<FWD, V, TM, TN, true>), pl.grid, dim3(256), 0, st, pl.a)
+    if (pl.vec) {
+        if (pl.TM == 2) GM_F32_L(true, 2, 2); else GM_F32_L(true, 1, 1);
+    } else {
+        if (pl.TM == 2) GM_F32_L(false, 2, 2); else GM_F32_L(false, 1, 1);
+    }
+#undef GM_F32_L
+}
+
 }  // namespace
+
+// gm_conv2d_f32_affine, terms = 0 (the entry and its argument checks: abi.hip)
+int conv_f32_affine_exact(const gm_conv_f32* p, const float* coef, const float* residual, int relu, void* scratch,
+                          size_t scratch_bytes, void* stream) {
+    Plan pl;
+    int rc = make_plan(p, pl, "gm_conv2d_f32_affine");
+    if (rc) return rc;
+    if ((rc = affine_args(pl, p, coef, residual, relu, scratch, scratch_bytes))) return rc;
+    hipStream_t st = as_stream(stream);
+    launch_affine(pl, st);
+    if ((rc = check_launch("k_conv_f32<affine>"))) return rc;
+    return affine_sum(pl, st);
+}
+
 }  // namespace gm
 
 using namespace gm;

@@ -27,6 +27,10 @@ struct F32Args {
     int ktiles, kt_per_split;      // k-tiles in total / per split (blockIdx.z)
     float* part;                   // splits > 1: [splits][M][N] fp32 slabs
     FastDiv fd_C, fd_S, fd_K, fd_Q, fd_P, fd_W, fd_H, fd_st;
+    // the forward-only affine epilogue (gm_conv2d_f32_affine; read by the AFF forms alone)
+    const float* coef;             // [2][N]: sc then sh (gm_bn_infer_coef's layout)
+    const float* residual;         // out's layout, may be null, may be out itself
+    int relu;
 };
 
 // ---- operand element access --------------------------------------------------
@@ -108,6 +112,38 @@ __global__ __launch_bounds__(256) void k_conv_f32_splitk_sum(const float* __rest
     }
 }
 
+// The eval-mode BatchNorm (+ residual, + ReLU) on an fp32 accumulator: k_bn_apply's fp32
+// arithmetic term for term (batchnorm.hip), so a convolution that ends in it equals the
+// convolution followed by gm_bn_fwd_infer_f32 bit for bit.  The fma is explicit: no
+// contraction setting can change it.  The residual may be the output buffer: element o
+// is read and then written by this thread alone.
+__device__ __forceinline__ float affine_epilogue(float v, float sc, float sh, const float* residual, size_t o,
+                                                 int relu) {
+    v = fmaf(v, sc, sh);
+    if (residual) v += residual[o];
+    return relu ? relu_nan(v) : v;
+}
+
+// splits > 1, affine form: out[i] = epilogue(sum_s part[s][i]) with column n = i mod N; the
+// sum is k_conv_f32_splitk_sum's, term for term.  residual and out may alias (no __restrict__).
+__global__ __launch_bounds__(256) void k_conv_f32_splitk_sum_affine(const float* __restrict__ part, int splits,
+                                                                   long long n, int N,
+                                                                   const float* __restrict__ coef,
+                                                                   const float* residual, int relu, float* out) {
+    long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long long stride = (long long)gridDim.x * 256;
+    unsigned c = (unsigned)(i % N);       // the one division; the column then steps with the index
+    const unsigned cstep = (unsigned)(stride % N);
+    for (; i < n; i += stride) {
+        float v = 0.f;
+        for (int s = 0; s < splits; ++s) v += part[(size_t)s * n + i];
+        out[i] = affine_epilogue(v, coef[c], coef[N + c], residual, (size_t)i, relu);
+        c += cstep;
+        if (c >= (unsigned)N) c -= (unsigned)N;
+    }
+}
+
 struct Plan {
     F32Args a;
     int TM, TN, splits;
@@ -185,6 +221,32 @@ inline int make_plan(const gm_conv_f32* p, Plan& pl, const char* fn) {
     pl.grid = dim3((unsigned)((M + BM - 1) / BM), (unsigned)((N + BN - 1) / BN), (unsigned)splits);
     pl.scratch = splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
     return GM_OK;
+}
+
+// gm_conv2d_f32_affine after its plan: the scratch check and the kernel arguments (the
+// descriptor's mode / accumulate / addend and the pointers were checked by the entry, abi.hip)
+inline int affine_args(Plan& pl, const gm_conv_f32* p, const float* coef, const float* residual, int relu,
+                       void* scratch, size_t scratch_bytes) {
+    if (pl.scratch && (!scratch || scratch_bytes < pl.scratch)) {
+        set_error("gm_conv2d_f32_affine: scratch %zu bytes < required %zu", scratch_bytes, pl.scratch);
+        return GM_E_SCRATCH;
+    }
+    pl.a.x = p->x; pl.a.w = p->w; pl.a.dy = nullptr; pl.a.out = p->out; pl.a.addend = nullptr;
+    pl.a.accumulate = 0;
+    pl.a.part = static_cast<float*>(scratch);
+    pl.a.coef = coef; pl.a.residual = residual; pl.a.relu = relu != 0;
+    return GM_OK;
+}
+
+// the split reduction's end of an affine launch (nothing to do for an unsplit plan)
+inline int affine_sum(const Plan& pl, hipStream_t st) {
+    if (pl.splits <= 1) return GM_OK;
+    const long long n = (long long)pl.a.M * pl.a.N;
+    long long g = (n + 1023) / 1024;
+    if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(k_conv_f32_splitk_sum_affine, dim3((unsigned)(g < 1 ? 1 : g)), dim3(256), 0, st, pl.a.part,
+                       pl.splits, n, pl.a.N, pl.a.coef, pl.a.residual, pl.a.relu, pl.a.out);
+    return check_launch("k_conv_f32_splitk_sum_affine");
 }
 
 }  // namespace

@@ -101,8 +101,10 @@ __device__ __forceinline__ void st_parts(uint16_t* tile, int plane_stride, int r
 
 // ---- the kernel ------------------------------------------------------------------
 // TERMS: 3 or 6.  VEC: 16-byte operand loads (C % 4 == 0 and K % 4 == 0), else element loads.
-template <int MODE, int TERMS, bool VEC, int TM, int TN>
+// AFF (FWD only): the affine epilogue of gm_conv2d_f32_affine (affine_epilogue, conv_f32_common.h).
+template <int MODE, int TERMS, bool VEC, int TM, int TN, bool AFF = false>
 __global__ __launch_bounds__(256) void k_conv_f32s(F32Args a) {
+    static_assert(!AFF || MODE == FWD, "the affine epilogue is a forward form");
     constexpr int NP = TERMS == 3 ? 2 : 3;
     constexpr int BM = 64 * TM, BN = 64 * TN;
     constexpr int V = VEC ? 4 : 1;
@@ -312,13 +314,20 @@ __global__ __launch_bounds__(256) void k_conv_f32s(F32Args a) {
         for (int j = 0; j < TN; ++j) {
             const int n = n0 + wn * 32 * TN + j * 32 + li;
             if (n >= a.N) continue;
+            float sc = 0.f, sh = 0.f;  // AFF: the lane's column coefficients, once per 32-column block
+            if (AFF && !split) {
+                sc = a.coef[n];
+                sh = a.coef[a.N + n];
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
                 if (m >= a.M) continue;
                 const size_t o = (size_t)m * a.N + n;
                 float v = acc[i][j][r];
-                if (!split) {
+                if (AFF) {  // (split: the sum kernel applies it)
+                    if (!split) v = affine_epilogue(v, sc, sh, a.residual, o, a.relu);
+                } else if (!split) {
                     if (a.addend) v += a.addend[o];
                     if (a.accumulate) v += dst[o];
                 }
@@ -382,6 +391,22 @@ void launch(const Plan& pl, hipStream_t st) {
 }
 
 template <int TERMS>
+void launch_affine(const Plan& pl, hipStream_t st) {
+#define GM_F32S_L(V, TM, TN) \
+    hipLaunchKernelGGL((k_conv_f32s<FWD, TERMS, V, TM, TN, true>), pl.grid, dim3(256), 0, st, pl.a)
+    if (pl.vec) {
+        if (pl.TM == 2 && pl.TN == 2) GM_F32S_L(true, 2, 2);
+        else if (pl.TM == 2) GM_F32S_L(true, 2, 1);
+        else GM_F32S_L(true, 1, 1);
+    } else {
+        if (pl.TM == 2 && pl.TN == 2) GM_F32S_L(false, 2, 2);
+        else if (pl.TM == 2) GM_F32S_L(false, 2, 1);
+        else GM_F32S_L(false, 1, 1);
+    }
+#undef GM_F32S_L
+}
+
+template <int TERMS>
 void launch_mode(int mode, const Plan& pl, hipStream_t st) {
     if (mode == FWD) launch<FWD, TERMS>(pl, st);
     else if (mode == DGRAD) launch<DGRAD, TERMS>(pl, st);
@@ -389,6 +414,21 @@ void launch_mode(int mode, const Plan& pl, hipStream_t st) {
 }
 
 }  // namespace
+
+// gm_conv2d_f32_affine, terms = 3 / 6 (the entry and its argument checks: abi.hip)
+int conv_f32_affine_split(const gm_conv_f32* p, int terms, const float* coef, const float* residual, int relu,
+                          void* scratch, size_t scratch_bytes, void* stream) {
+    Plan pl;
+    int rc = make_plan_split(p, terms, pl, "gm_conv2d_f32_affine");
+    if (rc) return rc;
+    if ((rc = affine_args(pl, p, coef, residual, relu, scratch, scratch_bytes))) return rc;
+    hipStream_t st = as_stream(stream);
+    if (terms == 3) launch_affine<3>(pl, st);
+    else launch_affine<6>(pl, st);
+    if ((rc = check_launch("k_conv_f32s<affine>"))) return rc;
+    return affine_sum(pl, st);
+}
+
 }  // namespace gm
 
 using namespace gm;

@@ -128,6 +128,12 @@ int usable_cus(int cus);                       // cus - reserved (at least cus /
 unsigned bn_faults_read(bool clear);           // batchnorm.hip
 unsigned conv_faults_read(bool clear);         // conv_igemm.hip
 
+// ---- gm_conv2d_f32_affine (abi.hip) by contraction: conv_f32.hip / conv_f32_split.hip ----
+int conv_f32_affine_exact(const gm_conv_f32* p, const float* coef, const float* residual, int relu, void* scratch,
+                          size_t scratch_bytes, void* stream);
+int conv_f32_affine_split(const gm_conv_f32* p, int terms, const float* coef, const float* residual, int relu,
+                          void* scratch, size_t scratch_bytes, void* stream);
+
 // ---- cross-workgroup hand-off without fences (cdna_hip_programming.md, in-launch
 // split-K recipe, sc1 form): the producer writes with sc1 (write-through) stores,
 // drains vmcnt, barriers and publishes with a relaxed agent-scope atomic; the

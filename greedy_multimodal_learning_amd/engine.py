@@ -734,9 +734,18 @@ class EvalStep:
     tensors - with graphs the graph's static outputs, valid until the next call.
 
     compute_dtype=torch.float32: the module forward in eval mode (f32_contraction as set on the
-    model) under the same interface, with the device-side metrics; never captured."""
+    model) under the same interface, with the device-side metrics; never captured.
 
-    def __init__(self, model, compute_dtype=torch.bfloat16, graphs=True):
+    compute_dtype=torch.float32, f32_trunk="fused": the fp32 eval trunk (vtrunk.EvalTrunkF32: each
+    view's convolutions with their BatchNorm, residual add and ReLU in the epilogue, bit for bit the
+    module path's convolution + gm_bn_fwd_infer_f32; exact or split-bf16 per GMConv2d.f32_terms as
+    begin() finds it), the MMTM sites and the heads through the calls the module forward makes for
+    fp32 eval input (the unstacked site call, then _fused_head, else _head): logits, squeezed maps
+    and site state are the module path's, torch.equal.  Everything runs on the current stream, so
+    with graphs=True a batch is captured as one chain and replayed as the bf16 form is.  The
+    default f32_trunk="modules" is the line above; "fused" with bf16 is a ValueError."""
+
+    def __init__(self, model, compute_dtype=torch.bfloat16, graphs=True, f32_trunk="modules"):
         from .model import MMTM_MVCNN, MMTM_MVCNN_N
         if not isinstance(model, (MMTM_MVCNN, MMTM_MVCNN_N)):
             raise TypeError("EvalStep: MMTM_MVCNN or MMTM_MVCNN_N")
@@ -744,8 +753,14 @@ class EvalStep:
             raise ValueError("EvalStep: compute_dtype must be torch.bfloat16 or torch.float32")
         self.model = model
         self.compute_dtype = compute_dtype
+        if f32_trunk not in ("modules", "fused"):
+            raise ValueError(f"EvalStep: f32_trunk must be 'modules' or 'fused' (got {f32_trunk!r})")
+        if f32_trunk == "fused" and compute_dtype != torch.float32:
+            raise ValueError(f"EvalStep: f32_trunk='fused' needs compute_dtype=torch.float32 (got {compute_dtype})")
+        self.f32_trunk = f32_trunk
         self.fused = compute_dtype == torch.bfloat16
-        self.graphs = bool(graphs) and self.fused
+        self.fused_f32 = f32_trunk == "fused"
+        self.graphs = bool(graphs) and (self.fused or self.fused_f32)
         self.two_view = isinstance(model, MMTM_MVCNN)
         self.nviews = 2 if self.two_view else model.num_views
         self.nets = [getattr(model, f"net_view_{i}") for i in range(self.nviews)]
@@ -753,7 +768,8 @@ class EvalStep:
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
             raise L.GreedyMMLError("EvalStep: the model must be on a HIP device")
-        self.trunk = vtrunk.EvalTrunk(self.nets) if self.fused else None
+        self.trunk = (vtrunk.EvalTrunk(self.nets) if self.fused else
+                      vtrunk.EvalTrunkF32(self.nets) if self.fused_f32 else None)
         self.acc = torch.zeros(3 + self.nviews, device=self.device, dtype=torch.int64)
         self._graphs, self._static, self._seen = {}, {}, set()
         self._gpool = None
@@ -783,9 +799,10 @@ class EvalStep:
         self._gpool = None
 
     def begin(self):
-        """Start a pass: the bf16 weight copies and the BatchNorm coefficient table from the
-        model's current parameters and buffers; the accumulators zeroed."""
-        if self.fused:
+        """Start a pass: the trunk's weight copies (bf16, or fp32 KRSC on the fp32 trunk), the
+        BatchNorm coefficient table and, on the fp32 trunk, each convolution's contraction mode
+        from the model as it is now; the accumulators zeroed."""
+        if self.trunk is not None:
             self.trunk.refresh()
         self.acc.zero_()
 
@@ -802,6 +819,8 @@ class EvalStep:
     def _forward(self, x, curation):
         m = self.model
         cm, caring = bool(curation[0]), curation[1]
+        if self.fused_f32:
+            return self._forward_f32(x, cm, caring)
         if not self.fused:
             was = m.training
             m.eval()
@@ -835,6 +854,34 @@ class EvalStep:
                 outs = [n.fc(torch.flatten(n.avgpool(f), 1)) for n, f in zip(self.nets, fs)]
         return list(outs), squeezed
 
+    def _forward_f32(self, x, cm, caring):
+        """MMTM_MVCNN.forward / MMTM_MVCNN_N.forward for fp32 eval input with the trunk segments on
+        the fp32 eval trunk: the same site and head calls, every launch on the current stream."""
+        from .model import MMTM_MVCNN
+        m, tr = self.model, self.trunk
+        if x.dtype != torch.float32:
+            raise ValueError(f"EvalStep(f32_trunk='fused'): fp32 input (got {x.dtype})")
+        rec = m.saving_mmtm_squeeze_array
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):
+            fs = [tr.layer(g, 1, tr.stem(g, x[:, g])) for g in range(self.nviews)]
+            squeezed = []
+            for i in (2, 3, 4):
+                fs = [tr.layer(g, i, f) for g, f in enumerate(fs)]
+                site = getattr(m, f"mmtm{i}")
+                if self.two_view:
+                    f0, f1, _, sq = site(fs[0], fs[1], False, rec, turnoff_cross_modal_flow=bool(m.mmtm_off),
+                                         average_squeezemaps=m.mmtm_rescale[i - 1] if m.mmtm_off else None,
+                                         curation_mode=cm, caring_modality=caring, on_device=True)
+                    fs = [f0, f1]
+                else:
+                    fs, _, sq = site(fs, False, rec, curation_mode=cm,
+                                     caring_modality=caring if caring is not None else 0, on_device=True)
+                squeezed.append(sq)
+            outs = MMTM_MVCNN._fused_head(self.nets, fs)
+            if outs is None:
+                outs = [MMTM_MVCNN._head(n, f) for n, f in zip(self.nets, fs)]
+        return list(outs), squeezed
+
     def _batch(self, x, y, curation):
         """Forward and metrics of one batch on the current stream; (outs, squeezed)."""
         outs, squeezed = self._forward(x, curation)
@@ -855,7 +902,9 @@ class EvalStep:
         cm = bool(curation[0])
         return (tuple(x.shape), tuple(x.stride()), x.dtype, cm, curation[1] if cm else None,
                 bool(getattr(self.model, "mmtm_off", False)),
-                bool(getattr(self.model, "saving_mmtm_squeeze_array", False)))
+                bool(getattr(self.model, "saving_mmtm_squeeze_array", False)),
+                # the fp32 trunk picks its kernels by the contraction modes begin() found
+                tuple(p.terms for p in self.trunk.pos) if self.fused_f32 else None)
 
     def _capture(self, key, curation):
         steps = [(m, m.step) for m in self._mmtms]

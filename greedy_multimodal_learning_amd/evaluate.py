@@ -35,12 +35,15 @@ def load_pretrained(model, path):
 @configurable
 def evalution_loop(model, loss_function, metrics, config, save_path, test=None, test_steps=None, use_gpu=True,
                    device_numbers=[0], custom_callbacks=[], pretrained_weights_path=None, save_with_structure=False,
-                   nummodalities=2, compute_dtype="fp32", f32_contraction="exact", eval_engine="modules"):
+                   nummodalities=2, compute_dtype="fp32", f32_contraction="exact", eval_engine="modules",
+                   eval_f32_trunk="modules"):
     """Reference src/training_loop.py:161-200 (one evaluation epoch, `test_*` keys).
     Runs in fp32 by default (the reference's arithmetic: its recorded averages feed the
     turn-off evaluation); `f32_contraction` ('exact', 'bf16x3', 'bf16x6') is set on every
     GMConv2d as the engine sets it (fp32 only).  `eval_engine`: "modules" (the default) or
-    "fused" (an engine.EvalStep runs the pass: train.eval_engine_arg)."""
+    "fused" (an engine.EvalStep runs the pass: train.eval_engine_arg).  `eval_f32_trunk`: "modules"
+    (the default) or "fused" (with eval_engine "fused" and fp32: the fp32 eval trunk, BatchNorms in
+    the convolution epilogues, results bit-identical to the module forward)."""
     from .conv import set_f32_contraction
     cdt = _DTYPES[compute_dtype]
     set_f32_contraction(model, f32_contraction_arg(cdt, f32_contraction), cdt)
@@ -56,7 +59,7 @@ def evalution_loop(model, loss_function, metrics, config, save_path, test=None, 
         c.set_config(config)
     logs = evaluate(model, test, "test", _DTYPES[compute_dtype], test_steps,
                     record_squeezed=bool(getattr(model, "saving_mmtm_squeeze_array", False)),
-                    engine=eval_engine_arg(model, cdt, eval_engine))
+                    engine=eval_engine_arg(model, cdt, eval_engine, f32_trunk=eval_f32_trunk))
     logs["epoch"] = 0
     H = {k: [v] for k, v in logs.items()}
     save_history(H, hist_dir, save_with_structure=save_with_structure)

@@ -335,7 +335,8 @@ class MMTM_N(nn.Module):
         return scales, squeeze
 
     def forward(self, xs, return_scale=False, return_squeezed_mps=False, turnoff_cross_modal_flow=False,
-                average_squeezemaps=None, curation_mode=False, caring_modality=0):
+                average_squeezemaps=None, curation_mode=False, caring_modality=0, on_device=False):
+        """on_device: as forward_stacked (engine.EvalStep's fp32 form)."""
         xs = list(xs)
         if len(xs) != self.N:
             raise ValueError(f"expected {self.N} modalities, got {len(xs)}")
@@ -352,5 +353,5 @@ class MMTM_N(nn.Module):
                                    curation_mode, caring_modality)
         outs = _MMTMNFunction.apply(cfg, self.fc_squeeze.weight, self.fc_squeeze.bias, *xs, *w_e, *b_e)
         ys, es, sq = list(outs[:self.N]), list(outs[self.N:2 * self.N]), outs[2 * self.N]
-        scales, squeeze = self._record(es, sq, return_scale, return_squeezed_mps)
+        scales, squeeze = self._record(es, sq, return_scale, return_squeezed_mps, on_device)
         return ys, scales, squeeze

@@ -54,15 +54,22 @@ def f32_contraction_arg(compute_dtype, f32_contraction):
     return f32_contraction
 
 
-def eval_engine_arg(model, compute_dtype, eval_engine, graphs=True):
+def eval_engine_arg(model, compute_dtype, eval_engine, graphs=True, f32_trunk="modules"):
     """The gin key `eval_engine` as evaluate()'s engine: None for "modules" (the module forward),
-    an engine.EvalStep over `model` (already on its device) for "fused"."""
+    an engine.EvalStep over `model` (already on its device) for "fused".  `f32_trunk` (the gin key
+    `eval_f32_trunk`): "modules", or "fused" - the fp32 eval trunk with the BatchNorms in the
+    convolution epilogues - which needs eval_engine "fused" and fp32."""
+    if f32_trunk not in ("modules", "fused"):
+        raise ValueError(f"eval_f32_trunk must be 'modules' or 'fused' (got {f32_trunk!r})")
+    if f32_trunk == "fused" and (eval_engine != "fused" or compute_dtype != torch.float32):
+        raise ValueError("eval_f32_trunk='fused' needs eval_engine='fused' and compute_dtype='fp32' "
+                         f"(got eval_engine={eval_engine!r}, {compute_dtype})")
     if eval_engine == "modules":
         return None
     if eval_engine != "fused":
         raise ValueError(f"eval_engine must be 'modules' or 'fused' (got {eval_engine!r})")
     from .engine import EvalStep
-    return EvalStep(model, compute_dtype=compute_dtype, graphs=graphs)
+    return EvalStep(model, compute_dtype=compute_dtype, graphs=graphs, f32_trunk=f32_trunk)
 
 
 def construct_callbacks(names):
@@ -175,7 +182,8 @@ def save_history(H, save_path, save_with_structure=True):
 def training_loop(model, loss_function, metrics, optimizer, config, save_path, steps_per_epoch, train=None,
                   valid=None, test=None, test_steps=None, validation_steps=None, use_gpu=True, device_numbers=[0],
                   custom_callbacks=[], checkpoint_monitor="val_acc", n_epochs=100, verbose=True, nummodalities=2,
-                  compute_dtype="fp32", graphs=True, f32_contraction="exact", eval_engine="modules"):
+                  compute_dtype="fp32", graphs=True, f32_contraction="exact", eval_engine="modules",
+                  eval_f32_trunk="modules"):
     """Reference src/training_loop.py:86-143 + Model_.train_loop (src/framework.py:
     250-330) on the fused engine.  `optimizer` is the (lr, momentum, wd) triple of the
     reference's SGD (only momentum = wd = 0, as every config uses, is fused; a torch SGD
@@ -189,7 +197,8 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
     `model_best_val.pt` (best `checkpoint_monitor`) and `model_last_epoch.pt` (every
     epoch) hold {'model', 'optimizer'} (src/training_loop.py:26-48, src/utils.py:107-115).
     `eval_engine`: "modules" (the default: the module forward in eval mode) or "fused" (an
-    engine.EvalStep runs the validation / test passes)."""
+    engine.EvalStep runs the validation / test passes).  `eval_f32_trunk`: "modules" (the
+    default) or "fused" (fp32 with eval_engine "fused" only: the fp32 eval trunk, eval_engine_arg)."""
     import math
 
     from .engine import BalancedStep
@@ -210,7 +219,7 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
     # the reference's optimizer object (never stepped: the engine's fused pass applies the
     # update with the learning rate read from it)
     opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=wd)
-    estep = eval_engine_arg(model, cdt, eval_engine, graphs)
+    estep = eval_engine_arg(model, cdt, eval_engine, graphs, f32_trunk=eval_f32_trunk)
     flags = step.flags  # the gate's model_pytoune; every other callback shares it
     flags.stop_training = False
     others = [c for c in custom_callbacks if c is not gate]

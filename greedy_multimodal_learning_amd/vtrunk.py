@@ -1045,3 +1045,130 @@ class EvalTrunk:
             else:
                 X = self._cbn(out, e["conv2"], residual=idt)
         return X
+
+
+class _EvalPosF32:
+    """One convolution + BatchNorm position of one view on the fp32 eval trunk: the modules, and
+    (from refresh()) the fp32 KRSC weight, the contraction and the [2][K] coefficient slice."""
+
+    def __init__(self, conv, bn):
+        self.conv, self.bn = conv, bn
+        self.K, self.C, self.R, self.S = conv.weight.shape
+        self.stride, self.pad = conv.stride[0], conv.padding[0]
+        self.w = self.coef = None
+        self.terms = 0
+
+
+class EvalTrunkF32:
+    """The trunks in eval mode on the reference's own arithmetic: fp32 NHWC, under torch.no_grad(),
+    one view at a time on the current stream (no view side streams: a captured batch is a single
+    chain of launches).  Every convolution carries its BatchNorm's running-statistics coefficients,
+    the block's residual add and its ReLU in its epilogue (conv.conv_f32_affine, exact-f32 MFMA or
+    split-bf16 as each GMConv2d.f32_terms says), which is bit for bit the module path's
+    convolution followed by gm_bn_fwd_infer_f32:
+
+        stem : conv1 with bn1 + ReLU, then the net's own max-pool module;
+        block: conv1 with bn1 + ReLU; the downsample convolution with its BatchNorm, no ReLU;
+               conv2 (conv3 of a Bottleneck) with its BatchNorm, the identity or downsample output
+               as the residual, and the ReLU.
+
+    refresh() reads the modules as they are now: one gm_bn_infer_coef launch over a table of every
+    BatchNorm of every view, each convolution's weight copied to an fp32 KRSC buffer, and its
+    f32_terms (conv.set_f32_contraction before a pass).  The coefficient table and the weight
+    buffers are allocated once and rewritten in place, so a captured batch's addresses stay valid
+    over refreshes; a changed f32_terms picks another kernel, which a captured batch does not see
+    (engine.EvalStep keys its graphs by the contraction modes).  The executor only reads the
+    modules."""
+
+    def __init__(self, nets):
+        from .bn import GMBatchNorm2d
+        from .conv import GMConv2d
+        self.nets = list(nets)
+        if not self.nets:
+            raise L.GreedyMMLError("EvalTrunkF32: at least one view")
+        sig = None
+        self.views = []  # per view: dict(stem=_EvalPosF32, 1..4 -> [dict(conv1=.., conv2=.., conv3=.., ds=..)])
+        self.pos = []
+        for n in self.nets:
+            mods = [m for m in n.modules() if isinstance(m, (GMConv2d, GMBatchNorm2d))]
+            s = [(type(m).__name__, tuple(m.weight.shape)) for m in mods]
+            if sig is not None and s != sig:
+                raise L.GreedyMMLError("EvalTrunkF32: the views must share one architecture")
+            sig = s
+            if any(isinstance(m, GMBatchNorm2d) and (not m.track_running_stats or not m.affine) for m in mods):
+                raise L.GreedyMMLError("EvalTrunkF32: affine BatchNorms with running statistics")
+            v = {"stem": _EvalPosF32(n.conv1, n.bn1)}
+            for i in (1, 2, 3, 4):
+                blks = []
+                for b in getattr(n, f"layer{i}"):
+                    e = {f"conv{k}": _EvalPosF32(getattr(b, f"conv{k}"), getattr(b, f"bn{k}"))
+                         for k in (1, 2, 3) if hasattr(b, f"conv{k}")}
+                    if b.downsample is not None:
+                        e["ds"] = _EvalPosF32(b.downsample[0], b.downsample[1])
+                    blks.append(e)
+                v[i] = blks
+            ps = [v["stem"]] + [p for i in (1, 2, 3, 4) for e in v[i] for p in e.values()]
+            for p in ps:
+                if not isinstance(p.conv, GMConv2d) or not p.conv._hip_ok() or not isinstance(p.bn, GMBatchNorm2d):
+                    raise L.GreedyMMLError("EvalTrunkF32: only the ResNet trunk's convolutions")
+            self.pos.extend(ps)
+            self.views.append(v)
+        self.coef = self._table = None
+
+    def refresh(self):
+        """BatchNorm coefficients, fp32 weights and contraction modes from the modules as they are now."""
+        lib = L.load()
+        dev = self.nets[0].conv1.weight.device
+        total = sum(2 * p.K for p in self.pos)
+        if self.coef is None or self.coef.device != dev or self.coef.numel() != total:
+            self.coef = torch.zeros(total, device=dev, dtype=torch.float32)
+        ents, off = [], 0
+        for p in self.pos:
+            bn = p.bn
+            if (bn.running_mean is None or any(t.dtype != torch.float32 for t in
+                                               (bn.running_mean, bn.running_var, bn.weight, bn.bias))):
+                raise L.GreedyMMLError("EvalTrunkF32: fp32 BatchNorm parameters and running statistics")
+            p.coef = self.coef[off:off + 2 * p.K]
+            off += 2 * p.K
+            ents.append(L.BnCoefEntry(bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                                      bn.running_var.data_ptr(), p.coef.data_ptr(), p.K, float(bn.eps)))
+            # a buffer kept for the executor's life: a captured batch holds its address
+            if p.w is None or p.w.device != dev:
+                p.w = torch.empty(p.K, p.C, p.R, p.S, device=dev, dtype=torch.float32, memory_format=CL)
+            p.w.copy_(p.conv.weight.detach())
+            p.terms = int(p.conv.f32_terms)
+        raw = bytes(L.arr(L.BnCoefEntry, ents))
+        if self._table is None or self._table.device != dev or self._table.numel() != len(raw):
+            self._table = torch.empty(len(raw), device=dev, dtype=torch.uint8)
+        self._table.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+        L.check(lib.gm_bn_infer_coef(self._table.data_ptr(), len(ents), max(e.C for e in ents), L.stream_of(dev)),
+                "gm_bn_infer_coef")
+
+    def _cbn(self, x, p, residual=None, relu=True):
+        from .conv import _desc, conv_f32_affine
+        if p.w is None:
+            raise L.GreedyMMLError("EvalTrunkF32: refresh() before the first batch")
+        N, C, H, W = x.shape
+        P, Q = (H + 2 * p.pad - p.R) // p.stride + 1, (W + 2 * p.pad - p.S) // p.stride + 1
+        out = torch.empty(N, p.K, P, Q, device=x.device, dtype=torch.float32, memory_format=CL)
+        return conv_f32_affine(_desc(N, H, W, C, p.K, p.R, p.S, p.stride, p.pad), x, p.w, out, p.coef,
+                               residual=residual, relu=relu, terms=p.terms)
+
+    def stem(self, g, x):
+        """layer-1 input of view g: maxpool(relu(bn1(conv1(x)))) for x [B, 3, H, W] fp32."""
+        if x.dtype != torch.float32 or not x.is_cuda:
+            raise L.GreedyMMLError("EvalTrunkF32: fp32 HIP input")
+        return self.nets[g].maxpool(self._cbn(_nhwc(x), self.views[g]["stem"]))
+
+    def layer(self, g, i, X):
+        """layer{i} of view g (BasicBlock.forward / Bottleneck.forward in eval mode)."""
+        X = _nhwc(X)
+        for e in self.views[g][i]:
+            idt = self._cbn(X, e["ds"], relu=False) if "ds" in e else X
+            out = self._cbn(X, e["conv1"])
+            if "conv3" in e:
+                out = self._cbn(out, e["conv2"])
+                X = self._cbn(out, e["conv3"], residual=idt)
+            else:
+                X = self._cbn(out, e["conv2"], residual=idt)
+        return X

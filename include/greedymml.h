@@ -566,6 +566,24 @@ int gm_conv2d_f32(const gm_conv_f32* p, void* scratch, size_t scratch_bytes, voi
 size_t gm_conv2d_f32_split_scratch(const gm_conv_f32* p, int terms);
 int gm_conv2d_f32_split(const gm_conv_f32* p, int terms, void* scratch, size_t scratch_bytes, void* stream);
 
+/* The forward convolution with an eval-mode BatchNorm, the block's residual add and its
+ * ReLU in the epilogue (the fp32 evaluation pass).  terms = 0: the exact-f32 MFMA
+ * (gm_conv2d_f32); 3 / 6: the split-bf16 contraction (gm_conv2d_f32_split); anything else
+ * is GM_E_ARG.  p->mode must be GM_CONV_FWD, p->accumulate 0 and p->addend NULL.  coef is
+ * fp32 [2][K], sc then sh, as gm_bn_infer_coef writes it (non-null, 4-byte aligned);
+ * residual is NULL or fp32 in out's layout and may be out itself.  On the fp32
+ * accumulator acc of output element o in channel k:
+ *     v = fmaf(acc, sc[k], sh[k]);   if (residual) v += residual[o];
+ *     if (relu) v = (v > 0 || v != v) ? v : 0;        (NaN passes, as torch.relu)
+ * which is gm_bn_fwd_infer_f32's arithmetic on the same accumulator (a split reduction
+ * applies it to the same fixed-order sum), so out equals gm_conv2d_f32 / gm_conv2d_f32_split
+ * followed by gm_bn_fwd_infer_f32 bit for bit.  Plan, tiles, splits and scratch are those
+ * of the unfused entry: scratch >= gm_conv2d_f32_scratch(p) (terms 0) or
+ * gm_conv2d_f32_split_scratch(p, terms) bytes, else GM_E_SCRATCH.  Everything is checked
+ * before anything is launched.  No allocation, no host sync; deterministic; capturable. */
+int gm_conv2d_f32_affine(const gm_conv_f32* p, int terms, const float* coef, const float* residual, int relu,
+                         void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------
  * BatchNorm2d (torchvision ResNet trunk, reference src/model.py:65-106 through
  * torchvision.models.resnet18), NHWC bf16 activations x[M][C] (M = N*H*W), fp32

@@ -8,11 +8,18 @@ weights, same batches: they must agree within the bf16 bar's effect), and whethe
 path is faster by more than the spread - the larger (max - min) of the two.
 
     python tools/eval_time.py [--workloads C2,C4,C5] [--batches 8] [--rounds 5] [--warmup 2]
-                              [--size 224] [--eager] [--label TEXT]
+                              [--size 224] [--eager] [--label TEXT] [--f32 [--contractions exact,bf16x3,bf16x6]]
 
 C2: 2 x ResNet-18, B = 64; C4: 4 x ResNet-18, B = 64; C5: 12 x ResNet-50, B = 32 (bench.py's
 workloads), bf16, the loader's view-major channels_last input layout.  No GPU, no number: the
 tool fails without a HIP device.
+
+--f32: the fp32 evaluation pass instead - the fp32 module path against EvalStep(torch.float32,
+f32_trunk="fused") (BatchNorm, residual and ReLU in the fp32 convolution epilogues), one line per
+contraction mode (conv.set_f32_contraction on the same model and batches, the two paths
+alternating within each mode).  The two paths compute the same bits, so each line also says
+whether the two passes' losses and accuracies agree ("same_metrics": loss within 1e-6 relative -
+a device fp64 sum against a host float sum - and equal accuracy).
 """
 import argparse
 import json
@@ -30,7 +37,7 @@ WORKLOADS = {"C2": dict(views=2, trunk="resnet18", batch=64), "C4": dict(views=4
              "C5": dict(views=12, trunk="resnet50", batch=32)}
 
 
-def make(name, size, nbatches, dev, batch=None):
+def make(name, size, nbatches, dev, batch=None, dtype=torch.bfloat16):
     from greedy_multimodal_learning_amd.bn import GMBatchNorm2d
     from greedy_multimodal_learning_amd.model import MMTM_MVCNN, MMTM_MVCNN_N
     w = WORKLOADS[name]
@@ -45,7 +52,7 @@ def make(name, size, nbatches, dev, batch=None):
                 m.running_var.copy_(0.5 + torch.rand(m.running_var.shape, device=dev, generator=g))
     loader = []
     for i in range(nbatches):
-        x = torch.randn(w["views"], B, size, size, 3, device=dev, generator=g).bfloat16().permute(1, 0, 4, 2, 3)
+        x = torch.randn(w["views"], B, size, size, 3, device=dev, generator=g).to(dtype).permute(1, 0, 4, 2, 3)
         y = torch.randint(0, 40, (B,), device=dev, generator=g)
         loader.append((torch.arange(i * B, (i + 1) * B), x, y))
     return model, loader
@@ -61,6 +68,8 @@ def main():
     ap.add_argument("--size", type=int, default=224)
     ap.add_argument("--eager", action="store_true", help="no hipGraph capture of the fused batch")
     ap.add_argument("--label", default="", help="copied into the output line (which tree, which run)")
+    ap.add_argument("--f32", action="store_true", help="the fp32 pass: module path against f32_trunk='fused'")
+    ap.add_argument("--contractions", default="exact,bf16x3,bf16x6", help="--f32: the contraction modes to time")
     a = ap.parse_args()
     if a.rounds < 5:
         ap.error("--rounds must be at least 5")
@@ -68,11 +77,15 @@ def main():
         sys.exit("eval_time.py: no HIP device (a pass is only timed on the GPU)")
     from greedy_multimodal_learning_amd.engine import EvalStep
     from greedy_multimodal_learning_amd.train import evaluate
+    from greedy_multimodal_learning_amd.conv import set_f32_contraction
     dev = torch.device("cuda:0")
-    BF = torch.bfloat16
-    for name in a.workloads.split(","):
-        model, loader = make(name, a.size, a.batches, dev, a.batch)
-        step = EvalStep(model, compute_dtype=BF, graphs=not a.eager)
+    BF = torch.float32 if a.f32 else torch.bfloat16  # the pass's compute dtype
+    cases = [(n, c) for n in a.workloads.split(",") for c in (a.contractions.split(",") if a.f32 else [None])]
+    for name, contraction in cases:
+        model, loader = make(name, a.size, a.batches, dev, a.batch, BF)
+        if a.f32:
+            set_f32_contraction(model, contraction, BF)
+        step = EvalStep(model, compute_dtype=BF, graphs=not a.eager, f32_trunk="fused" if a.f32 else "modules")
         paths = {"modules": lambda: evaluate(model, loader, "val", BF),
                  "fused": lambda: evaluate(model, loader, "val", BF, engine=step)}
         logs = {}
@@ -91,6 +104,8 @@ def main():
         out = {"tool": "eval_time", "label": a.label, "workload": name, "batch": len(loader[0][2]), "size": a.size,
                "batches_per_pass": len(loader), "rounds": a.rounds, "graphs": bool(step.graphs),
                "graph_replays": step.replays, "capture_failures": step.capture_failures}
+        if a.f32:
+            out.update(compute_dtype="fp32", f32_contraction=contraction, f32_trunk="fused", warmup=a.warmup)
         for k, ts in times.items():
             out[k] = {"ms_per_batch_median": round(statistics.median(ts), 4), "min": round(min(ts), 4),
                       "max": round(max(ts), 4), "val_loss": float(logs[k]["val_loss"]),
@@ -100,6 +115,10 @@ def main():
         out["spread_ms"] = round(spread, 4)
         out["fused_faster_by_more_than_spread"] = bool(gain > spread)
         out["speedup"] = round(out["modules"]["ms_per_batch_median"] / out["fused"]["ms_per_batch_median"], 3)
+        if a.f32:
+            lm, lf = out["modules"]["val_loss"], out["fused"]["val_loss"]
+            out["same_metrics"] = bool(abs(lm - lf) <= 1e-6 * abs(lm)
+                                       and abs(out["modules"]["val_acc"] - out["fused"]["val_acc"]) <= 1e-4)
         print(json.dumps(out), flush=True)
         del model, loader, step, paths
         torch.cuda.empty_cache()
