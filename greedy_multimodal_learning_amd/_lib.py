@@ -292,6 +292,15 @@ EXPORTS.update({
     "gm_bn_bwd_stats_coef_offset": (c_size_t, [c_int, c_int, c_int]),
     "gm_bn_bwd_stats_finalize_grouped": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "gm_bn_bwd_apply_grouped_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "gm_bn_fold_blocks": (c_int, [ctypes.c_longlong, c_int, c_int, c_int]),
+    "gm_bn_fwd_finalize_apply_grouped_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "gm_bn_fwd_finalize_apply_grouped_bf16_ex": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "gm_bn_bwd_finalize_apply_grouped_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "gm_bn_bwd_finalize_apply_grouped_bf16_ex": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "gm_bn_fwd_finalize_apply_res_affine_grouped_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                                                 c_void_p, c_int, c_void_p]),
+    "gm_bn_fwd_finalize_apply_res_affine_grouped_bf16_ex": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                                                    c_void_p, c_int, c_int, c_void_p]),
     "gm_maxpool2d_bwd_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 })
 

@@ -323,64 +323,109 @@ __device__ __forceinline__ FinOps fin_load(const ReduceArgs& a, int c) {
     return f;
 }
 
+// The per-channel arithmetic of finalize() on its own (fp64, one rounding to fp32 per output):
+// every kernel that finalizes - the ticketed last block, the redundant combine, the
+// statistics finalizes and the folded finalize + apply kernels, whose blocks other than the
+// first keep the coefficients and store nothing - computes its coefficients here.
+struct FwdCoef {
+    float sc, sh, mean, invstd, rmean, rvar;
+};
+struct BwdCoef {
+    float ca, cb, cc, c3, dg, db;
+};
+
+__device__ __forceinline__ FwdCoef fwd_coef(const ReduceArgs& a, double S1, double S2, double invM, const FinOps& f) {
+    FwdCoef k;
+    const double g = (double)f.g;
+    const double mean = S1 * invM;
+    double var = S2 * invM - mean * mean;
+    if (var < 0.0) var = 0.0;
+    const double invstd = 1.0 / sqrt(var + (double)a.eps);
+    const double sc = g * invstd;
+    k.sc = (float)sc;
+    k.sh = (float)((double)f.b - mean * sc);
+    k.mean = (float)mean;
+    k.invstd = (float)invstd;
+    const double m = (double)a.momentum;
+    const double unb = a.M > 1 ? var * (double)a.M / (double)(a.M - 1) : var;
+    k.rmean = (float)((1.0 - m) * (double)f.rm + m * mean);
+    k.rvar = (float)((1.0 - m) * (double)f.rv + m * unb);
+    return k;
+}
+
+template <bool CENTER>
+__device__ __forceinline__ BwdCoef bwd_coef(double S1, double S2, double invM, const FinOps& f) {
+    BwdCoef k;
+    const double g = (double)f.g;
+    const double mean = (double)f.rm;
+    const double is = (double)f.rv;
+    const double ca = g * is;
+    const double cb = -g * is * is * is * S2 * invM;
+    k.ca = (float)ca;
+    k.cb = (float)cb;
+    if (CENTER) {  // dx = ca*dz + cb*(x - mean) + cc (fp32 path: no cb*x - cb*mean cancellation)
+        k.cc = (float)(-ca * S1 * invM);
+        k.c3 = (float)mean;
+    } else {
+        k.cc = (float)(-ca * S1 * invM - cb * mean);
+        k.c3 = 0.f;
+    }
+    k.dg = (float)(S2 * is);
+    k.db = (float)S1;
+    return k;
+}
+
+// the side outputs of a finalize: statistics, running averages, coefficient area(s) (FWD);
+// coefficient area and parameter gradients (BWD)
+template <bool SC1>
+__device__ __forceinline__ void fwd_store(const ReduceArgs& a, int c, const FwdCoef& k) {
+    const int C = a.C;
+    a.coef[c] = k.sc;
+    a.coef[C + c] = k.sh;
+    if (SC1) {
+        st_sc1(&a.coef[c], k.sc);
+        st_sc1(&a.coef[C + c], k.sh);
+    }
+    if (a.coef_out) {
+        a.coef_out[c] = k.sc;
+        a.coef_out[C + c] = k.sh;
+    }
+    a.save_mean[c] = k.mean;
+    a.save_invstd[c] = k.invstd;
+    if (a.rmean) {
+        a.rmean[c] = k.rmean;
+        a.rvar[c] = k.rvar;
+    }
+}
+
+template <bool SC1, bool CENTER>
+__device__ __forceinline__ void bwd_store(const ReduceArgs& a, int c, const BwdCoef& k) {
+    const int C = a.C;
+    a.coef[c] = k.ca;
+    a.coef[C + c] = k.cb;
+    a.coef[2 * C + c] = k.cc;
+    if (CENTER) a.coef[3 * C + c] = k.c3;
+    if (SC1) {
+        st_sc1(&a.coef[c], k.ca);
+        st_sc1(&a.coef[C + c], k.cb);
+        st_sc1(&a.coef[2 * C + c], k.cc);
+    }
+    if (a.accumulate) {
+        a.dgamma[c] += k.dg;
+        a.dbeta[c] += k.db;
+    } else {
+        a.dgamma[c] = k.dg;
+        a.dbeta[c] = k.db;
+    }
+}
+
 // SC1: the coefficients are published with write-through stores (read by the other
 // blocks of the same launch in the fused forward, k_bn_fwd_fused)
 template <int MODE, bool SC1 = false, bool CENTER = false>
 __device__ __forceinline__ void finalize(const ReduceArgs& a, int c, double S1, double S2, double invM,
                                          const FinOps& f) {
-    const int C = a.C;
-    const double g = (double)f.g;
-    if (MODE == FWD) {
-        const double mean = S1 * invM;
-        double var = S2 * invM - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const double invstd = 1.0 / sqrt(var + (double)a.eps);
-        const double sc = g * invstd;
-        a.coef[c] = (float)sc;
-        a.coef[C + c] = (float)((double)f.b - mean * sc);
-        if (SC1) {
-            st_sc1(&a.coef[c], a.coef[c]);
-            st_sc1(&a.coef[C + c], a.coef[C + c]);
-        }
-        if (a.coef_out) {
-            a.coef_out[c] = a.coef[c];
-            a.coef_out[C + c] = a.coef[C + c];
-        }
-        a.save_mean[c] = (float)mean;
-        a.save_invstd[c] = (float)invstd;
-        if (a.rmean) {
-            const double m = (double)a.momentum;
-            const double unb = a.M > 1 ? var * (double)a.M / (double)(a.M - 1) : var;
-            a.rmean[c] = (float)((1.0 - m) * (double)f.rm + m * mean);
-            a.rvar[c] = (float)((1.0 - m) * (double)f.rv + m * unb);
-        }
-    } else {
-        const double mean = (double)f.rm;
-        const double is = (double)f.rv;
-        const double ca = g * is;
-        const double cb = -g * is * is * is * S2 * invM;
-        a.coef[c] = (float)ca;
-        a.coef[C + c] = (float)cb;
-        if (CENTER) {  // dx = ca*dz + cb*(x - mean) + cc (fp32 path: no cb*x - cb*mean cancellation)
-            a.coef[2 * C + c] = (float)(-ca * S1 * invM);
-            a.coef[3 * C + c] = (float)mean;
-        } else {
-            a.coef[2 * C + c] = (float)(-ca * S1 * invM - cb * mean);
-        }
-        if (SC1) {
-            st_sc1(&a.coef[c], a.coef[c]);
-            st_sc1(&a.coef[C + c], a.coef[C + c]);
-            st_sc1(&a.coef[2 * C + c], a.coef[2 * C + c]);
-        }
-        const float dg = (float)(S2 * is), db = (float)S1;
-        if (a.accumulate) {
-            a.dgamma[c] += dg;
-            a.dbeta[c] += db;
-        } else {
-            a.dgamma[c] = dg;
-            a.dbeta[c] = db;
-        }
-    }
+    if (MODE == FWD) fwd_store<SC1>(a, c, fwd_coef(a, S1, S2, invM, f));
+    else bwd_store<SC1, CENTER>(a, c, bwd_coef<CENTER>(S1, S2, invM, f));
 }
 
 // Cross-workgroup hand-off without fences (cdna_hip_programming.md, in-launch
@@ -767,22 +812,21 @@ __global__ __launch_bounds__(kT) void k_stem_pool_bn_bwd(ReduceArgs a0, StemPool
 // convolution writes one per 64-pixel slab - and the combine sits on the forward's critical
 // path), fp64, then the row groups combined in a fixed order.
 constexpr int kFinT = 1024;
-__global__ __launch_bounds__(kFinT) void k_bn_stats_finalize(ReduceArgs a0) {
-    const ReduceArgs a = group_args(a0);
-    __shared__ double rd[kFinT / 32][128];
-    const int t = threadIdx.x, cs = blockIdx.y;  // channel slice cs (64 channels)
+__device__ __forceinline__ void load_coef(const float* p, int cg, float* c);
+
+// the residual-affine form's residual: r <- bf16(fmaf(r, sc, sh)) as floats, the 8 values a
+// BatchNorm apply without ReLU stores (pack8's rounding) and the consuming apply reads back
+__device__ __forceinline__ void res_affine(float* r, const float* sc, const float* sh) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = fmaf(r[j], sc[j], sh[j]);
+    unpack8(pack8(r), r);
+}
+
+// the combine of the finalize kernels: sums of slice cs's nrc partial rows, (S1, S2) of channel
+// cs * 64 + t in the threads t < 64 (rd: the block's [32][128] fp64 LDS)
+__device__ __forceinline__ void fin_combine(const ReduceArgs& a, int cs, double (*rd)[128], double& S1, double& S2) {
+    const int t = threadIdx.x;
     const int lv = t & 31, rg = t >> 5;
-    FinOps fo;
-    {  // every thread, no branch (a conditional load here cost wave 0 a waited round trip
-       // before its row loads); threads t >= 64 load channel t % 64's again, unused
-        const int c = cs * 64 + (t & 63);
-        const float* rm = a.rmean ? a.rmean : a.gamma;
-        const float* rv = a.rmean ? a.rvar : a.gamma;
-        fo.g = a.gamma[c];
-        fo.b = a.beta[c];
-        fo.rm = rm[c];
-        fo.rv = rv[c];
-    }
     const float4* rows = reinterpret_cast<const float4*>(a.part + (size_t)cs * a.nrc * 128);
     double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0;
     for (int i0 = rg; i0 < a.nrc; i0 += 8 * 32) {
@@ -797,12 +841,39 @@ __global__ __launch_bounds__(kFinT) void k_bn_stats_finalize(ReduceArgs a0) {
     }
     rd[rg][4 * lv] = d0; rd[rg][4 * lv + 1] = d1; rd[rg][4 * lv + 2] = d2; rd[rg][4 * lv + 3] = d3;
     __syncthreads();
+    S1 = 0.0;
+    S2 = 0.0;
     if (t < 64) {
-        double S1 = 0.0, S2 = 0.0;
         for (int i = 0; i < kFinT / 32; ++i) {
             S1 += rd[i][2 * t];
             S2 += rd[i][2 * t + 1];
         }
+    }
+}
+
+// the forward finalize's per-channel operands: every thread, no branch (a conditional load
+// here cost wave 0 a waited round trip before its row loads); threads t >= 64 load channel
+// t % 64's again, unused
+__device__ __forceinline__ FinOps fin_load_fwd_all(const ReduceArgs& a, int cs) {
+    FinOps fo;
+    const int c = cs * 64 + (threadIdx.x & 63);
+    const float* rm = a.rmean ? a.rmean : a.gamma;
+    const float* rv = a.rmean ? a.rvar : a.gamma;
+    fo.g = a.gamma[c];
+    fo.b = a.beta[c];
+    fo.rm = rm[c];
+    fo.rv = rv[c];
+    return fo;
+}
+
+__global__ __launch_bounds__(kFinT) void k_bn_stats_finalize(ReduceArgs a0) {
+    const ReduceArgs a = group_args(a0);
+    __shared__ double rd[kFinT / 32][128];
+    const int t = threadIdx.x, cs = blockIdx.y;  // channel slice cs (64 channels)
+    const FinOps fo = fin_load_fwd_all(a, cs);
+    double S1, S2;
+    fin_combine(a, cs, rd, S1, S2);
+    if (t < 64) {
         finalize<FWD>(a, cs * 64 + t, S1, S2, 1.0 / (double)a.M, fo);  // (rm / rv unused without rmean)
         if (a.nbt && cs == 0 && t == 0) *a.nbt += 1;
     }
@@ -818,29 +889,229 @@ __global__ __launch_bounds__(kFinT) void k_bn_bwd_stats_finalize(ReduceArgs a0, 
     a.coef = coef0 + blockIdx.z * cstride;
     __shared__ double rd[kFinT / 32][128];
     const int t = threadIdx.x, cs = blockIdx.y;
-    const int lv = t & 31, rg = t >> 5;
     const FinOps fo = fin_load<BWD>(a, cs * 64 + (t & 63));  // every thread: no branch, no early wait
-    const float4* rows = reinterpret_cast<const float4*>(a.part + (size_t)cs * a.nrc * 128);
-    double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0;
-    for (int i0 = rg; i0 < a.nrc; i0 += 8 * 32) {
-        float4 v[8];  // clamped rows, all eight loads in flight, then the value select (a
-#pragma unroll    // conditional load compiled to a branch and a full wait per row)
-        for (int u = 0; u < 8; ++u) v[u] = rows[(size_t)min(i0 + u * 32, a.nrc - 1) * 32 + lv];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            if (i0 + u * 32 >= a.nrc) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            d0 += (double)v[u].x; d1 += (double)v[u].y; d2 += (double)v[u].z; d3 += (double)v[u].w;
+    double S1, S2;
+    fin_combine(a, cs, rd, S1, S2);
+    if (t < 64) finalize<BWD>(a, cs * 64 + t, S1, S2, 1.0 / (double)a.M, fo);
+}
+
+// Finalize and apply in one launch (gm_bn_fwd_finalize_apply_grouped_bf16): grid (nb, C / 64, G).
+// Every block of (slice cs, group g) combines the slice's partial rows itself - fin_combine and
+// fwd_coef, k_bn_stats_finalize's own code, so all nb blocks hold the same coefficients bit for
+// bit - keeps sc / sh in LDS and streams its share of the slice's 128-byte channel band with
+// k_bn_apply's per-element arithmetic: 8 threads per pixel, four 16-B loads in flight per
+// thread, the block's 128-pixel chunks bx, bx + nb, ...  Only block bx == 0 of a slice stores
+// the finalize's side outputs (statistics, running averages, coef_out, the coefficient area), and
+// only (bx, cs) == (0, 0) the counter.  No block waits for another: the redundant combine costs
+// nb * rows * 512 B of L2 reads per (slice, group), which fold_blocks() bounds.
+// RAFF (the residual-affine form, gm_bn_fwd_finalize_apply_res_affine_grouped_bf16): the residual
+// is the raw output of a downsample convolution and rb its own BatchNorm (no ReLU), whose apply
+// pass is not run: the block combines that BatchNorm's rows too (one launch finalizes both, the
+// side outputs of both from block 0) and adds bf16(fmaf(r, sc_r, sh_r)) - the value that
+// BatchNorm's apply would have stored, rounded as it stores it - so every output bit is the same.
+struct ResBn {
+    int nrc;                        // the residual BatchNorm's partial rows per slice
+    float momentum, eps;
+    float* part;                    // group 0's rows; its coefficient area follows them
+    unsigned long long scr_stride;  // bytes between the groups' row + coefficient blocks
+    struct Grp {
+        const float* gamma;
+        const float* beta;
+        float* rmean;
+        float* rvar;
+        float* save_mean;
+        float* save_invstd;
+        long long* nbt;
+        float* coef_out;
+    } grp[kMaxBnG];
+};
+
+// a (this block's group) with the residual BatchNorm's parameters, statistics and rows
+__device__ __forceinline__ ReduceArgs res_bn_args(const ReduceArgs& a, const ResBn& rb) {
+    ReduceArgs r = a;
+    const ResBn::Grp& q = rb.grp[blockIdx.z];
+    r.nrc = rb.nrc; r.momentum = rb.momentum; r.eps = rb.eps;
+    r.part = reinterpret_cast<float*>(reinterpret_cast<char*>(rb.part) + blockIdx.z * rb.scr_stride);
+    r.coef = r.part + (size_t)rb.nrc * 2 * a.C;
+    r.gamma = q.gamma; r.beta = q.beta; r.rmean = q.rmean; r.rvar = q.rvar;
+    r.save_mean = q.save_mean; r.save_invstd = q.save_invstd; r.nbt = q.nbt; r.coef_out = q.coef_out;
+    return r;
+}
+
+template <bool RES, bool RELU, bool RAFF>
+__device__ __forceinline__ void finalize_apply_body(const ReduceArgs& a0, const ResBn* rb) {
+    const ReduceArgs a = group_args(a0);
+    __shared__ double rd[kFinT / 32][128];
+    __shared__ float cf[RAFF ? 4 : 2][64];
+    const int t = threadIdx.x, cs = blockIdx.y;
+    const FinOps fo = fin_load_fwd_all(a, cs);
+    double S1, S2;
+    fin_combine(a, cs, rd, S1, S2);
+    if (t < 64) {
+        const FwdCoef k = fwd_coef(a, S1, S2, 1.0 / (double)a.M, fo);
+        cf[0][t] = k.sc;
+        cf[1][t] = k.sh;
+        if (blockIdx.x == 0) {
+            fwd_store<false>(a, cs * 64 + t, k);
+            if (a.nbt && cs == 0 && t == 0) *a.nbt += 1;
         }
     }
-    rd[rg][4 * lv] = d0; rd[rg][4 * lv + 1] = d1; rd[rg][4 * lv + 2] = d2; rd[rg][4 * lv + 3] = d3;
     __syncthreads();
-    if (t < 64) {
-        double S1 = 0.0, S2 = 0.0;
-        for (int i = 0; i < kFinT / 32; ++i) {
-            S1 += rd[i][2 * t];
-            S2 += rd[i][2 * t + 1];
+    if (RAFF) {  // the residual's BatchNorm: the same combine and finalize on its own rows
+        const ReduceArgs ar = res_bn_args(a, *rb);
+        const FinOps fr = fin_load_fwd_all(ar, cs);
+        fin_combine(ar, cs, rd, S1, S2);  // (rd is free: every thread is past the barrier above)
+        if (t < 64) {
+            const FwdCoef k = fwd_coef(ar, S1, S2, 1.0 / (double)ar.M, fr);
+            cf[2][t] = k.sc;
+            cf[3][t] = k.sh;
+            if (blockIdx.x == 0) {
+                fwd_store<false>(ar, cs * 64 + t, k);
+                if (ar.nbt && cs == 0 && t == 0) *ar.nbt += 1;
+            }
         }
-        finalize<BWD>(a, cs * 64 + t, S1, S2, 1.0 / (double)a.M, fo);
+        __syncthreads();
+    }
+    const int j8 = (t & 7) * 8;
+    float sc[8], sh[8], rsc[8], rsh[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        sc[j] = cf[0][j8 + j];
+        sh[j] = cf[1][j8 + j];
+        if (RAFF) {
+            rsc[j] = cf[2][j8 + j];
+            rsh[j] = cf[3][j8 + j];
+        }
+    }
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    // 32-bit vector offsets off a uniform base (the host checks M * C < 2^31): this thread's
+    // vector of pixel p is p * vpr + (t & 7) of the slice's band
+    const unsigned vpr = (unsigned)a.C >> 3, M = (unsigned)a.M;
+    const u32x4* XX = static_cast<const u32x4*>(a.x) + cs * 8;
+    const u32x4* RR = reinterpret_cast<const u32x4*>(a.res) + cs * 8;
+    uint4* YY = a.yout + cs * 8;
+    uint8_t* MM = a.mask_out ? a.mask_out + cs * 8 : nullptr;
+    auto fin = [&](unsigned i, u32x4 wx, u32x4 wr) {
+        float f[8], r[8];
+        unpack8(make_uint4(wx.x, wx.y, wx.z, wx.w), f);
+        if (RES) unpack8(make_uint4(wr.x, wr.y, wr.z, wr.w), r);
+        if (RAFF) res_affine(r, rsc, rsh);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float z = fmaf(f[j], sc[j], sh[j]);
+            if (RES) z += r[j];
+            f[j] = RELU ? relu_nan(z) : z;
+        }
+        const uint4 o = pack8(f);
+        YY[i] = o;
+        if (RES && RELU && MM) MM[i] = (uint8_t)mask_byte(o);
+    };
+    constexpr unsigned U = 4;
+    const unsigned st = gridDim.x * (kFinT / 8);  // pixels per grid pass
+    unsigned p = blockIdx.x * (kFinT / 8) + (t >> 3);
+    const unsigned lane = t & 7;
+    // one loop, the ragged last batch predicated (pixels past M load pixel p's vector again and
+    // store nothing); M + 4 st < 2^32: no wrap
+    for (; p < M; p += U * st) {
+        u32x4 rx[U], rr[U];
+#pragma unroll
+        for (unsigned u = 0; u < U; ++u) {
+            const unsigned q = p + u * st < M ? p + u * st : p;
+            rx[u] = XX[q * vpr + lane];
+            if (RES) rr[u] = RR[q * vpr + lane];
+        }
+#pragma unroll
+        for (unsigned u = 0; u < U; ++u) {
+            asm volatile("" : "+v"(rx[u]));
+            if (RES) asm volatile("" : "+v"(rr[u]));
+        }
+#pragma unroll
+        for (unsigned u = 0; u < U; ++u)
+            if (p + u * st < M) fin((p + u * st) * vpr + lane, rx[u], RES ? rr[u] : rx[u]);
+    }
+}
+
+template <bool RES, bool RELU>
+__global__ __launch_bounds__(kFinT) void k_bn_finalize_apply(ReduceArgs a0) {
+    finalize_apply_body<RES, RELU, false>(a0, nullptr);
+}
+
+template <bool RELU>
+__global__ __launch_bounds__(kFinT) void k_bn_finalize_apply_raff(ReduceArgs a0, ResBn rb) {
+    finalize_apply_body<true, RELU, true>(a0, &rb);
+}
+
+// The same fold for the backward from producer statistics (gm_bn_bwd_finalize_apply_grouped_bf16):
+// k_bn_bwd_stats_finalize's combine and bwd_coef in every block, then k_bn_apply_bwd<RELU, false,
+// MASKX = RELU>'s arithmetic over the block's share of the band.  Block bx == 0 of a slice alone
+// writes dgamma / dbeta (accumulate honoured) and the ca / cb / cc coefficient area.
+template <bool RELU>
+__global__ __launch_bounds__(kFinT) void k_bn_bwd_finalize_apply(ReduceArgs a0, float* coef0, long long cstride) {
+    ReduceArgs a = group_args(a0);
+    a.coef = coef0 + blockIdx.z * cstride;
+    __shared__ double rd[kFinT / 32][128];
+    __shared__ float cf[3][64];
+    const int t = threadIdx.x, cs = blockIdx.y;
+    const FinOps fo = fin_load<BWD>(a, cs * 64 + (t & 63));
+    const int j8 = (t & 7) * 8;
+    double S1, S2;
+    fin_combine(a, cs, rd, S1, S2);
+    float fs[8], fh[8];
+    if (RELU) {  // the forward's coefficients: in flight over the coefficient arithmetic
+        load_coef(a.fcoef, cs * 8 + (t & 7), fs);
+        load_coef(a.fcoef + a.C, cs * 8 + (t & 7), fh);
+    }
+    if (t < 64) {
+        const BwdCoef k = bwd_coef<false>(S1, S2, 1.0 / (double)a.M, fo);
+        cf[0][t] = k.ca;
+        cf[1][t] = k.cb;
+        cf[2][t] = k.cc;
+        if (blockIdx.x == 0) bwd_store<false, false>(a, cs * 64 + t, k);
+    }
+    __syncthreads();
+    float ca[8], cb[8], cc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        ca[j] = cf[0][j8 + j];
+        cb[j] = cf[1][j8 + j];
+        cc[j] = cf[2][j8 + j];
+    }
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const unsigned vpr = (unsigned)a.C >> 3, M = (unsigned)a.M;  // 32-bit offsets as k_bn_finalize_apply
+    const u32x4* DY = static_cast<const u32x4*>(a.dy) + cs * 8;
+    const u32x4* XX = static_cast<const u32x4*>(a.x) + cs * 8;
+    uint4* DX = a.yout + cs * 8;
+    auto out = [&](unsigned i, u32x4 wd, u32x4 wx) {
+        float d[8], xf[8], o[8];
+        unpack8(make_uint4(wd.x, wd.y, wd.z, wd.w), d);
+        unpack8(make_uint4(wx.x, wx.y, wx.z, wx.w), xf);
+        if (RELU) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) d[j] = fmaf(xf[j], fs[j], fh[j]) > 0.f ? d[j] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = fmaf(ca[j], d[j], fmaf(cb[j], xf[j], cc[j]));
+        DX[i] = pack8(o);
+    };
+    constexpr unsigned U = 4;
+    const unsigned st = gridDim.x * (kFinT / 8);
+    unsigned p = blockIdx.x * (kFinT / 8) + (t >> 3);
+    const unsigned lane = t & 7;
+    for (; p < M; p += U * st) {  // the ragged last batch predicated, as k_bn_finalize_apply
+        u32x4 rdy[U], rx[U];
+#pragma unroll
+        for (unsigned u = 0; u < U; ++u) {
+            const unsigned q = p + u * st < M ? p + u * st : p;
+            rdy[u] = DY[q * vpr + lane];
+            rx[u] = XX[q * vpr + lane];
+        }
+#pragma unroll
+        for (unsigned u = 0; u < U; ++u) asm volatile("" : "+v"(rdy[u]), "+v"(rx[u]));
+#pragma unroll
+        for (unsigned u = 0; u < U; ++u) {
+            if (p + u * st < M) out((p + u * st) * vpr + lane, rdy[u], rx[u]);
+            __builtin_amdgcn_sched_barrier(0);  // one vector's arithmetic at a time: 128 VGPRs, no scratch
+        }
     }
 }
 
@@ -1395,6 +1666,8 @@ struct ApplyArgs {
     long long cgs;       // vectors and its coefficients cgs floats after group 0's
     long long fcgs;      // bwd MASKX: group g's fcoef fcgs floats after group 0's
     uint8_t* mask_out;   // fwd (relu + residual), optional: the ReLU mask bytes (as gvec)
+    const float* rcoef;  // fwd RAFF: the residual BatchNorm's sc[C], sh[C]
+    long long rcgs;      // and group g's rcgs floats after group 0's
 };
 
 __device__ __forceinline__ void load_coef(const float* p, int cg, float* c) {
@@ -1403,7 +1676,7 @@ __device__ __forceinline__ void load_coef(const float* p, int cg, float* c) {
     c[0] = a.x; c[1] = a.y; c[2] = a.z; c[3] = a.w; c[4] = b.x; c[5] = b.y; c[6] = b.z; c[7] = b.w;
 }
 
-template <bool RES, bool RELU, typename E>
+template <bool RES, bool RELU, typename E, bool RAFF = false>
 __global__ __launch_bounds__(kT) void k_bn_apply(ApplyArgs a) {
     const long long stride = (long long)gridDim.x * kT;  // multiple of C/8
     long long v = (long long)blockIdx.x * kT + threadIdx.x;
@@ -1413,7 +1686,13 @@ __global__ __launch_bounds__(kT) void k_bn_apply(ApplyArgs a) {
     float sc[8], sh[8];
     load_coef(coef, cg, sc);
     load_coef(coef + a.C, cg, sh);
-    auto fin = [&](long long i, float* f, const float* r) {
+    float rsc[8], rsh[8];
+    if (RAFF) {  // the residual's own BatchNorm coefficients (res_affine)
+        load_coef(a.rcoef + blockIdx.y * a.rcgs, cg, rsc);
+        load_coef(a.rcoef + blockIdx.y * a.rcgs + a.C, cg, rsh);
+    }
+    auto fin = [&](long long i, float* f, float* r) {
+        if (RAFF) res_affine(r, rsc, rsh);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float z = fmaf(f[j], sc[j], sh[j]);
@@ -2161,6 +2440,50 @@ extern "C" int gm_bn_relu_maxpool2d_bwd_stats_grouped_bf16(const gm_pool_desc* d
     return stem_pool_bwd(d, G, dy_pool, idx, xsel, ps, scratch, bytes, false, bcoef, bcoef_gs, stream, fn);
 }
 
+// the kernel arguments of the finalizes from producer partial rows (and of the folded finalize +
+// apply kernels, which also read the apply's tensors from grp[])
+static void fwd_stats_args(gm::ReduceArgs& a, const gm_bn_fwd* ps, int G, float* stats, int rows) {
+    const int C = ps[0].C;
+    a.M = ps[0].M; a.C = C; a.SW = 64; a.tpr_log = 3; a.nrc = rows;
+    a.momentum = ps[0].momentum; a.eps = ps[0].eps;
+    a.part = stats;
+    a.coef = stats + (size_t)rows * 2 * C;
+    a.scr_stride = (unsigned long long)(rows + 1) * 2 * C * sizeof(float);
+    a.hdr_words = 0;
+    for (int g = 0; g < G; ++g) {
+        gm::BnGroup& q = a.grp[g];
+        q.x = ps[g].x;
+        q.gamma = ps[g].gamma; q.beta = ps[g].beta;
+        q.rmean = ps[g].running_mean; q.rvar = ps[g].running_var;
+        q.save_mean = ps[g].save_mean; q.save_invstd = ps[g].save_invstd;
+        q.nbt = ps[g].num_batches_tracked;
+        q.coef_out = ps[g].coef_out;
+        q.res = static_cast<const uint4*>(ps[g].residual);
+        q.yout = static_cast<uint4*>(ps[g].y);
+        q.mask_out = static_cast<uint8_t*>(ps[g].relu_mask);
+    }
+}
+
+static void bwd_stats_args(gm::ReduceArgs& a, const gm_bn_bwd* ps, int G, float* stats, int rows) {
+    const int C = ps[0].C;
+    a.M = ps[0].M; a.C = C; a.SW = 64; a.tpr_log = 3; a.nrc = rows;
+    a.accumulate = ps[0].accumulate;
+    a.part = stats;
+    a.coef = stats;
+    a.scr_stride = (unsigned long long)(rows + 1) * 2 * C * sizeof(float);
+    a.hdr_words = 0;
+    for (int g = 0; g < G; ++g) {
+        gm::BnGroup& q = a.grp[g];
+        q.x = ps[g].x; q.dy = ps[g].dy;
+        q.gamma = ps[g].gamma;
+        q.save_mean = const_cast<float*>(ps[g].save_mean);
+        q.save_invstd = const_cast<float*>(ps[g].save_invstd);
+        q.dgamma = ps[g].dgamma; q.dbeta = ps[g].dbeta;
+        q.fcoef = ps[g].fwd_coef;
+        q.yout = static_cast<uint4*>(ps[g].dx);
+    }
+}
+
 // BatchNorm forward statistics from producer partial rows (gm_conv2d_fwd_grouped_bn_stats_bf16,
 // the stem's gm_conv2d_fwd_grouped_stats_bf16): stats = [G] x ([C / 64 slices][rows][64 x (sum,
 // sum of squares)] then 2C floats of coefficient scratch); ps[g] as for
@@ -2173,21 +2496,7 @@ extern "C" int gm_bn_fwd_stats_finalize_grouped(const gm_bn_fwd* ps, int G, floa
     GM_REQUIRE(stats && rows >= 1 && C >= 64 && C % 64 == 0 && ps[0].M >= 1, "%s: C a multiple of 64, rows >= 1",
                fn);
     ReduceArgs a{};
-    a.M = ps[0].M; a.C = C; a.SW = 64; a.tpr_log = 3; a.nrc = rows;
-    a.momentum = ps[0].momentum; a.eps = ps[0].eps;
-    a.part = stats;
-    a.coef = stats + (size_t)rows * 2 * C;
-    a.scr_stride = (unsigned long long)(rows + 1) * 2 * C * sizeof(float);
-    a.hdr_words = 0;
-    for (int g = 0; g < G; ++g) {
-        BnGroup& q = a.grp[g];
-        q.x = ps[g].x;
-        q.gamma = ps[g].gamma; q.beta = ps[g].beta;
-        q.rmean = ps[g].running_mean; q.rvar = ps[g].running_var;
-        q.save_mean = ps[g].save_mean; q.save_invstd = ps[g].save_invstd;
-        q.nbt = ps[g].num_batches_tracked;
-        q.coef_out = ps[g].coef_out;
-    }
+    fwd_stats_args(a, ps, G, stats, rows);
     hipLaunchKernelGGL(k_bn_stats_finalize, dim3(1, C / 64, G), dim3(kFinT), 0, as_stream(stream), a);
     return check_launch("k_bn_stats_finalize");
 }
@@ -2195,8 +2504,9 @@ extern "C" int gm_bn_fwd_stats_finalize_grouped(const gm_bn_fwd* ps, int G, floa
 // The apply after gm_bn_fwd_stats_finalize_grouped: y = relu?(x*sc + sh (+ residual)), the
 // coefficients read from the statistics buffer; one launch for the G groups when their
 // tensors are evenly strided (the view-batched trunk), else one per group.
-extern "C" int gm_bn_fwd_apply_grouped_bf16(const gm_bn_fwd* ps, int G, const float* stats, int rows, void* stream) {
-    const char* fn = "gm_bn_fwd_apply_grouped_bf16";
+// rstats / rrows: the residual-affine form (the residual BatchNorm's finalized statistics buffer)
+static int fwd_apply(const gm_bn_fwd* ps, int G, const float* stats, int rows, const float* rstats, int rrows,
+                     void* stream, const char* fn) {
     int rc = check_groups_fwd(ps, G, fn);
     if (rc) return rc;
     const gm_bn_fwd* p = ps;
@@ -2223,7 +2533,13 @@ extern "C" int gm_bn_fwd_apply_grouped_bf16(const gm_bn_fwd* ps, int G, const fl
         b.gvec = strided ? gs / 8 : 0;
         b.cgs = strided ? cgs : 0;
         const dim3 g(apply_grid(b.nvec, C), strided ? G : 1);
-        if (p->residual) {
+        if (rstats) {
+            const long long rcgs = (long long)(rrows + 1) * 2 * C;
+            b.rcoef = rstats + gi * rcgs + (size_t)rrows * 2 * C;
+            b.rcgs = strided ? rcgs : 0;
+            if (p->relu) hipLaunchKernelGGL((k_bn_apply<true, true, uint16_t, true>), g, dim3(kT), 0, st, b);
+            else hipLaunchKernelGGL((k_bn_apply<true, false, uint16_t, true>), g, dim3(kT), 0, st, b);
+        } else if (p->residual) {
             if (p->relu) hipLaunchKernelGGL((k_bn_apply<true, true, uint16_t>), g, dim3(kT), 0, st, b);
             else hipLaunchKernelGGL((k_bn_apply<true, false, uint16_t>), g, dim3(kT), 0, st, b);
         } else {
@@ -2233,6 +2549,10 @@ extern "C" int gm_bn_fwd_apply_grouped_bf16(const gm_bn_fwd* ps, int G, const fl
         if ((rc = check_launch("k_bn_apply"))) return rc;
     }
     return GM_OK;
+}
+
+extern "C" int gm_bn_fwd_apply_grouped_bf16(const gm_bn_fwd* ps, int G, const float* stats, int rows, void* stream) {
+    return fwd_apply(ps, G, stats, rows, nullptr, 0, stream, "gm_bn_fwd_apply_grouped_bf16");
 }
 
 // The BatchNorm backward from producer statistics (include/greedymml.h): stats as written by
@@ -2260,20 +2580,7 @@ extern "C" int gm_bn_bwd_stats_finalize_grouped(const gm_bn_bwd* ps, int G, floa
     if (rc) return rc;
     const int C = ps[0].C;
     ReduceArgs a{};
-    a.M = ps[0].M; a.C = C; a.SW = 64; a.tpr_log = 3; a.nrc = rows;
-    a.accumulate = ps[0].accumulate;
-    a.part = stats;
-    a.coef = stats;
-    a.scr_stride = (unsigned long long)(rows + 1) * 2 * C * sizeof(float);
-    a.hdr_words = 0;
-    for (int g = 0; g < G; ++g) {
-        BnGroup& q = a.grp[g];
-        q.x = ps[g].x; q.dy = ps[g].dy;
-        q.gamma = ps[g].gamma;
-        q.save_mean = const_cast<float*>(ps[g].save_mean);
-        q.save_invstd = const_cast<float*>(ps[g].save_invstd);
-        q.dgamma = ps[g].dgamma; q.dbeta = ps[g].dbeta;
-    }
+    bwd_stats_args(a, ps, G, stats, rows);
     float* coef0 = stats + gm_bn_bwd_stats_coef_offset(C, G, rows);
     hipLaunchKernelGGL(k_bn_bwd_stats_finalize, dim3(1, C / 64, G), dim3(kFinT), 0, as_stream(stream), a, coef0,
                        (long long)4 * C);
@@ -2312,4 +2619,154 @@ extern "C" int gm_bn_bwd_apply_grouped_bf16(const gm_bn_bwd* ps, int G, const fl
         if ((rc = check_launch("k_bn_apply_bwd"))) return rc;
     }
     return GM_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// Finalize folded into the apply (k_bn_finalize_apply / k_bn_bwd_finalize_apply).
+// The rule: blocks per (64-channel slice, group) of the folded launch, 0 = decline (the two
+// launches).  From the per-shape table of tools/bn_fold_probe.py: the
+// folded launch is fastest with about one 1024-thread block per CU over the whole grid
+// (nb * C / 64 * G ~ kFoldGrid; half of that or twice that lost 1 - 3 us at every trunk shape),
+// with at least two 128-pixel chunks per block, and it still won where every block re-reads
+// twice the slice's own x + y bytes of partial rows (nb * rows * 512 B against M * 256 B: the
+// downsample BatchNorm of layer 2, 784 rows), the largest share measured - so that is the bound.
+// Past 2^25 elements over the G groups (64 MiB of bf16) the apply is bound by its streaming, and
+// k_bn_apply's grid streams better than one 1024-thread block per CU: the largest shape that won
+// had 25.7 M elements (layer 1 at C2), the smallest that lost 38.5 M (layer 2 of ResNet-50, 12 views).
+constexpr int kFoldGrid = 256;
+constexpr int kFoldMaxRows = 1024;
+constexpr int kFoldReread = 2;
+constexpr long long kFoldMaxElems = 1ll << 25;
+
+extern "C" int gm_bn_fold_blocks(long long M, int C, int rows, int G) {
+    if (M < 1 || rows < 1 || rows > kFoldMaxRows || C < 64 || C % 64 != 0 || G < 1) return 0;
+    if (M * C >= (1ll << 31)) return 0;  // the folded kernels index a group's vectors in 32 bits
+    if (M * C * G > kFoldMaxElems) return 0;
+    long long nb = kFoldGrid / ((long long)(C / 64) * G);
+    if (nb < 1) nb = 1;
+    const long long by_pixels = (M + 255) / 256;  // <= the 4-vector work items (2 M per slice)
+    if (nb > by_pixels) nb = by_pixels;
+    const long long by_reread = (long long)kFoldReread * M * 256 / ((long long)rows * 512);
+    if (nb > by_reread) nb = by_reread;
+    return nb < 1 ? 0 : (int)nb;
+}
+
+static int fold_nb_arg(long long M, int C, int rows, int G, int nb, const char* fn) {
+    GM_REQUIRE(nb >= 0 && nb <= 65535, "%s: nb in 0 (the rule) .. 65535 (got %d)", fn, nb);
+    GM_REQUIRE(nb == 0 || M * C < (1ll << 31), "%s: nb > 0 needs M * C < 2^31", fn);
+    return nb > 0 ? nb : gm_bn_fold_blocks(M, C, rows, G);
+}
+
+// nb > 0: the folded kernel with that many blocks per (slice, group), whatever the rule says
+// (tests, tools/bn_fold_probe.py); nb == 0: the rule, and where it declines the two launches.
+extern "C" int gm_bn_fwd_finalize_apply_grouped_bf16_ex(const gm_bn_fwd* ps, int G, float* stats, int rows, int nb,
+                                                        void* stream) {
+    const char* fn = "gm_bn_fwd_finalize_apply_grouped_bf16_ex";
+    int rc = check_groups_fwd(ps, G, fn);
+    if (rc) return rc;
+    const int C = ps[0].C;
+    GM_REQUIRE(stats && rows >= 1 && C >= 64 && C % 64 == 0 && ps[0].M >= 1 && ps[0].y,
+               "%s: C a multiple of 64, rows >= 1, y", fn);
+    for (int g = 0; g < G; ++g)
+        GM_REQUIRE(!ps[g].relu_mask == !ps[0].relu_mask, "%s: relu_mask in all groups or none", fn);
+    nb = fold_nb_arg(ps[0].M, C, rows, G, nb, fn);
+    if (nb < 0) return nb;
+    if (nb == 0) {
+        if ((rc = gm_bn_fwd_stats_finalize_grouped(ps, G, stats, rows, stream))) return rc;
+        return gm_bn_fwd_apply_grouped_bf16(ps, G, stats, rows, stream);
+    }
+    ReduceArgs a{};
+    fwd_stats_args(a, ps, G, stats, rows);
+    const dim3 grid(nb, C / 64, G), blk(kFinT);
+    hipStream_t st = as_stream(stream);
+    if (ps[0].residual) {
+        if (ps[0].relu) hipLaunchKernelGGL((k_bn_finalize_apply<true, true>), grid, blk, 0, st, a);
+        else hipLaunchKernelGGL((k_bn_finalize_apply<true, false>), grid, blk, 0, st, a);
+    } else {
+        if (ps[0].relu) hipLaunchKernelGGL((k_bn_finalize_apply<false, true>), grid, blk, 0, st, a);
+        else hipLaunchKernelGGL((k_bn_finalize_apply<false, false>), grid, blk, 0, st, a);
+    }
+    return check_launch("k_bn_finalize_apply");
+}
+
+extern "C" int gm_bn_fwd_finalize_apply_grouped_bf16(const gm_bn_fwd* ps, int G, float* stats, int rows, void* stream) {
+    return gm_bn_fwd_finalize_apply_grouped_bf16_ex(ps, G, stats, rows, 0, stream);
+}
+
+// The residual-affine form (include/greedymml.h): ps[g].residual is the raw input of the BatchNorm
+// rps[g] (its x), which is finalized here too and never applied on its own.
+extern "C" int gm_bn_fwd_finalize_apply_res_affine_grouped_bf16_ex(const gm_bn_fwd* ps, int G, float* stats, int rows,
+                                                                   const gm_bn_fwd* rps, float* rstats, int rrows,
+                                                                   int nb, void* stream) {
+    const char* fn = "gm_bn_fwd_finalize_apply_res_affine_grouped_bf16_ex";
+    int rc = check_groups_fwd(ps, G, fn);
+    if (rc || (rc = check_groups_fwd(rps, G, fn))) return rc;
+    const int C = ps[0].C;
+    GM_REQUIRE(stats && rstats && rows >= 1 && rrows >= 1 && C >= 64 && C % 64 == 0 && ps[0].M >= 1 && ps[0].y,
+               "%s: C a multiple of 64, rows >= 1, y", fn);
+    for (int g = 0; g < G; ++g) {
+        GM_REQUIRE(!ps[g].relu_mask == !ps[0].relu_mask, "%s: relu_mask in all groups or none", fn);
+        GM_REQUIRE(ps[g].residual && rps[g].x == ps[g].residual && rps[g].M == ps[0].M && rps[g].C == C &&
+                       !rps[g].relu && !rps[g].residual,
+                   "%s: group %d: the residual must be its BatchNorm's input (same shape, no ReLU, no residual)",
+                   fn, g);
+    }
+    // both BatchNorms' rows are re-read by every block
+    nb = fold_nb_arg(ps[0].M, C, rows + rrows, G, nb, fn);
+    if (nb < 0) return nb;
+    if (nb == 0) {  // two finalizes and one apply: still no apply pass for the residual's BatchNorm
+        if ((rc = gm_bn_fwd_stats_finalize_grouped(ps, G, stats, rows, stream))) return rc;
+        if ((rc = gm_bn_fwd_stats_finalize_grouped(rps, G, rstats, rrows, stream))) return rc;
+        return fwd_apply(ps, G, stats, rows, rstats, rrows, stream, fn);
+    }
+    ReduceArgs a{};
+    fwd_stats_args(a, ps, G, stats, rows);
+    ResBn rb{};
+    rb.nrc = rrows; rb.momentum = rps[0].momentum; rb.eps = rps[0].eps;
+    rb.part = rstats;
+    rb.scr_stride = (unsigned long long)(rrows + 1) * 2 * C * sizeof(float);
+    for (int g = 0; g < G; ++g) {
+        ResBn::Grp& q = rb.grp[g];
+        q.gamma = rps[g].gamma; q.beta = rps[g].beta;
+        q.rmean = rps[g].running_mean; q.rvar = rps[g].running_var;
+        q.save_mean = rps[g].save_mean; q.save_invstd = rps[g].save_invstd;
+        q.nbt = rps[g].num_batches_tracked; q.coef_out = rps[g].coef_out;
+    }
+    const dim3 grid(nb, C / 64, G), blk(kFinT);
+    hipStream_t st = as_stream(stream);
+    if (ps[0].relu) hipLaunchKernelGGL(k_bn_finalize_apply_raff<true>, grid, blk, 0, st, a, rb);
+    else hipLaunchKernelGGL(k_bn_finalize_apply_raff<false>, grid, blk, 0, st, a, rb);
+    return check_launch("k_bn_finalize_apply_raff");
+}
+
+extern "C" int gm_bn_fwd_finalize_apply_res_affine_grouped_bf16(const gm_bn_fwd* ps, int G, float* stats, int rows,
+                                                                const gm_bn_fwd* rps, float* rstats, int rrows,
+                                                                void* stream) {
+    return gm_bn_fwd_finalize_apply_res_affine_grouped_bf16_ex(ps, G, stats, rows, rps, rstats, rrows, 0, stream);
+}
+
+extern "C" int gm_bn_bwd_finalize_apply_grouped_bf16_ex(const gm_bn_bwd* ps, int G, float* stats, int rows, int nb,
+                                                        void* stream) {
+    const char* fn = "gm_bn_bwd_finalize_apply_grouped_bf16_ex";
+    int rc = check_bwd_from_stats(ps, G, stats, rows, fn);
+    if (rc) return rc;
+    const int C = ps[0].C;
+    nb = fold_nb_arg(ps[0].M, C, rows, G, nb, fn);
+    if (nb < 0) return nb;
+    if (nb == 0) {
+        if ((rc = gm_bn_bwd_stats_finalize_grouped(ps, G, stats, rows, stream))) return rc;
+        return gm_bn_bwd_apply_grouped_bf16(ps, G, stats, rows, stream);
+    }
+    ReduceArgs a{};
+    bwd_stats_args(a, ps, G, stats, rows);
+    float* coef0 = stats + gm_bn_bwd_stats_coef_offset(C, G, rows);
+    const dim3 grid(nb, C / 64, G), blk(kFinT);
+    hipStream_t st = as_stream(stream);
+    if (ps[0].relu) hipLaunchKernelGGL(k_bn_bwd_finalize_apply<true>, grid, blk, 0, st, a, coef0, (long long)4 * C);
+    else hipLaunchKernelGGL(k_bn_bwd_finalize_apply<false>, grid, blk, 0, st, a, coef0, (long long)4 * C);
+    return check_launch("k_bn_bwd_finalize_apply");
+}
+
+extern "C" int gm_bn_bwd_finalize_apply_grouped_bf16(const gm_bn_bwd* ps, int G, float* stats, int rows, void* stream) {
+    return gm_bn_bwd_finalize_apply_grouped_bf16_ex(ps, G, stats, rows, 0, stream);
 }

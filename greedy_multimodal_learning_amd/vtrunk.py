@@ -69,6 +69,14 @@ IDT_MASKED_ADDEND = True
 # epilogue of the convolution it feeds, then one finalize + one streaming apply
 # (False: the single-launch backward)
 EPI_BN_BWD_STATS = True
+# those finalizes folded into their apply launch where gm_bn_fold_blocks takes the shape, bit for
+# bit the two launches (False: always the two launches)
+BN_FOLD = True
+# a downsample block's residual BatchNorm applied inside the block-output BatchNorm's apply
+# (gm_bn_fwd_finalize_apply_res_affine_grouped_bf16): no apply pass for it and no normalised
+# downsample tensor, every bit the same (False: the residual BatchNorm as a launch of its own).
+# Needs both convolutions' epilogue statistics, BN_RELU_MASK and DS_DZ_LINK (else the old path).
+DS_RES_AFFINE = True
 _GM_E_UNSUP = -3
 
 
@@ -425,8 +433,13 @@ def _bn_backward_from_stats(dz, xb, G, gammas, betas, sm, si, coef, part, rows, 
                              dbs[g].data_ptr(), int(acc), 0, coef[g].data_ptr(), 0))
     st = L.stream_of(xb.device)
     arr = L.arr(L.BnBwd, descs)
-    L.check(lib.gm_bn_bwd_stats_finalize_grouped(arr, G, part.data_ptr(), rows, st), "gm_bn_bwd_stats_finalize_grouped")
-    L.check(lib.gm_bn_bwd_apply_grouped_bf16(arr, G, part.data_ptr(), rows, st), "gm_bn_bwd_apply_grouped_bf16")
+    if BN_FOLD:  # one launch where gm_bn_fold_blocks takes the shape, else the same two
+        L.check(lib.gm_bn_bwd_finalize_apply_grouped_bf16(arr, G, part.data_ptr(), rows, st),
+                "gm_bn_bwd_finalize_apply_grouped_bf16")
+    else:
+        L.check(lib.gm_bn_bwd_stats_finalize_grouped(arr, G, part.data_ptr(), rows, st),
+                "gm_bn_bwd_stats_finalize_grouped")
+        L.check(lib.gm_bn_bwd_apply_grouped_bf16(arr, G, part.data_ptr(), rows, st), "gm_bn_bwd_apply_grouped_bf16")
     if sunk:
         for p in list(gammas) + list(betas):
             sink_done(p)
@@ -469,10 +482,15 @@ class _VBNFn(torch.autograd.Function):
         if stats is not None and "part" in stats:  # partial rows from the convolution's epilogue
             part, rows = stats.pop("part"), stats.pop("rows")
             st = L.stream_of(dev)
-            L.check(lib.gm_bn_fwd_stats_finalize_grouped(L.arr(L.BnFwd, descs), G, part.data_ptr(), rows, st),
-                    "gm_bn_fwd_stats_finalize_grouped")
-            L.check(lib.gm_bn_fwd_apply_grouped_bf16(L.arr(L.BnFwd, descs), G, part.data_ptr(), rows, st),
-                    "gm_bn_fwd_apply_grouped_bf16")
+            arr = L.arr(L.BnFwd, descs)
+            if BN_FOLD:  # one launch where gm_bn_fold_blocks takes the shape, else the same two
+                L.check(lib.gm_bn_fwd_finalize_apply_grouped_bf16(arr, G, part.data_ptr(), rows, st),
+                        "gm_bn_fwd_finalize_apply_grouped_bf16")
+            else:
+                L.check(lib.gm_bn_fwd_stats_finalize_grouped(arr, G, part.data_ptr(), rows, st),
+                        "gm_bn_fwd_stats_finalize_grouped")
+                L.check(lib.gm_bn_fwd_apply_grouped_bf16(arr, G, part.data_ptr(), rows, st),
+                        "gm_bn_fwd_apply_grouped_bf16")
         else:
             buf = _bn_scratch_g(dev, M, C, G)
             L.check(lib.gm_bn_fwd_train_grouped_bf16(L.arr(L.BnFwd, descs), G, buf.data_ptr(), buf.numel(),
@@ -547,6 +565,74 @@ def vbn(X, bns, residual=None, relu=False, residual_join=None, stats=None):
     with torch.autocast("cuda", enabled=False):
         return _VBNFn.apply(X, residual, len(bns), bns, bool(relu), join, stats,
                             *[b.weight for b in bns], *[b.bias for b in bns])
+
+
+class _VBlockOutFn(torch.autograd.Function):
+    """relu(BatchNorm_g(Z_g) + BatchNorm'_g(R_g)) per view group: the output of a downsample
+    block from the raw outputs Z of its last convolution and R of its downsample convolution,
+    both BatchNorms' statistics from those convolutions' epilogues (DS_RES_AFFINE)."""
+
+    @staticmethod
+    def forward(ctx, Z, R, G, bns, rbns, st, rst, *params):
+        lib = L.load()
+        gammas, betas, rgammas, rbetas = (params[i * G:(i + 1) * G] for i in range(4))
+        zb, rb = _nhwc(Z.to(BF)), _nhwc(R.to(BF))
+        GN, C, H, W = zb.shape
+        N = GN // G
+        M = N * H * W
+        dev = zb.device
+        y = torch.empty_like(zb, memory_format=CL)
+        sm, si, smr, sir = (torch.empty(G, C, device=dev, dtype=torch.float32) for _ in range(4))
+        ymask = torch.empty(GN * H * W * C // 8, device=dev, dtype=torch.uint8)
+        descs, rdescs = [], []
+        for g in range(G):
+            r = slice(g * N, (g + 1) * N)
+            bn, rbn = bns[g], rbns[g]
+            descs.append(L.BnFwd(M, C, 1, zb[r].data_ptr(), rb[r].data_ptr(), y[r].data_ptr(),
+                                 gammas[g].data_ptr(), betas[g].data_ptr(), L.ptr(bn.running_mean),
+                                 L.ptr(bn.running_var), float(bn.momentum), float(bn.eps), sm[g].data_ptr(),
+                                 si[g].data_ptr(), L.ptr(bn.num_batches_tracked), 0,
+                                 ymask[g * (M * C // 8):].data_ptr()))
+            rdescs.append(L.BnFwd(M, C, 0, rb[r].data_ptr(), 0, 0, rgammas[g].data_ptr(), rbetas[g].data_ptr(),
+                                  L.ptr(rbn.running_mean), L.ptr(rbn.running_var), float(rbn.momentum),
+                                  float(rbn.eps), smr[g].data_ptr(), sir[g].data_ptr(),
+                                  L.ptr(rbn.num_batches_tracked), 0, 0))
+        part, rows = st.pop("part"), st.pop("rows")
+        rpart, rrows = rst.pop("part"), rst.pop("rows")
+        L.check(lib.gm_bn_fwd_finalize_apply_res_affine_grouped_bf16(
+            L.arr(L.BnFwd, descs), G, part.data_ptr(), rows, L.arr(L.BnFwd, rdescs), rpart.data_ptr(), rrows,
+            L.stream_of(dev)), "gm_bn_fwd_finalize_apply_res_affine_grouped_bf16")
+        ctx.save_for_backward(zb, rb, y, ymask, sm, si, smr, sir, *params)
+        ctx.G = G
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        zb, rb, y, ymask, sm, si, smr, sir, *prm = ctx.saved_tensors
+        G = ctx.G
+        gammas, betas, rgammas, rbetas = (prm[i * G:(i + 1) * G] for i in range(4))
+        need = ctx.needs_input_grad
+        want = [any(need[7 + i * G:7 + (i + 1) * G]) for i in range(4)]
+        # the two backward launches of the separate BatchNorms (DS_DZ_LINK): the block output's, then
+        # the residual's on the same dy and ReLU mask
+        dyb = _nhwc(dy.to(BF))
+        dz, _, gw, gb = _bn_backward(dyb, y, zb, G, gammas, betas, sm, si, True, False, None, want[0], want[1],
+                                     ymask)
+        dr, _, rgw, rgb = _bn_backward(dyb, y, rb, G, rgammas, rbetas, smr, sir, True, False, None, want[2],
+                                       want[3], ymask)
+        return (dz if need[0] else None, dr if need[1] else None, None, None, None, None, None,
+                *gw, *gb, *rgw, *rgb)
+
+
+def vblock_out(Z, R, bns, rbns, st, rst):
+    """The output of a downsample block (DS_RES_AFFINE): see _VBlockOutFn."""
+    for group in (bns, rbns):
+        b0 = group[0]
+        if any(b.momentum is None or b.momentum != b0.momentum or b.eps != b0.eps for b in group):
+            raise L.GreedyMMLError("vtrunk BatchNorm: the views must share momentum and eps")
+    with torch.autocast("cuda", enabled=False):
+        return _VBlockOutFn.apply(Z, R, len(bns), bns, rbns, st, rst, *[b.weight for b in bns],
+                                  *[b.bias for b in bns], *[b.weight for b in rbns], *[b.bias for b in rbns])
 
 
 # ---- stem: 7x7/s2 convolution on the pixel-pair view, BN + ReLU + max-pool --------------
@@ -786,19 +872,33 @@ def vblock(blocks, X):
         st = {"dgrad_link": link_in, "bn_link": link_out, "dz_link": res_link, "res_link": res_link}
         return vbn(vconv(x, convs, cjoin, stats=st), bns, stats=st, **kw)
     rl = {} if ds else None
-    if ds:
-        idt = cbn(X, [b.downsample[0] for b in blocks], [b.downsample[1] for b in blocks], join, res_link=rl)
+    dsbns = [b.downsample[1] for b in blocks] if ds else None
+    raw = None  # (downsample convolution output, its statistics): its BatchNorm joins the block output's
+    if ds and DS_RES_AFFINE and DS_DZ_LINK and BN_RELU_MASK:
+        rst = {"dgrad_link": None, "bn_link": None, "dz_link": rl, "res_link": rl}
+        raw = (vconv(X, [b.downsample[0] for b in blocks], join, stats=rst), rst)
+        idt = None
+    elif ds:
+        idt = cbn(X, [b.downsample[0] for b in blocks], dsbns, join, res_link=rl)
     else:
         idt = X
+
+    def out_bn(x, convs, bns, link_in):
+        if raw is None:
+            return cbn(x, convs, bns, link_in=link_in, residual=idt, relu=True,
+                       residual_join=None if ds else join, res_link=rl)
+        st = {"dgrad_link": link_in, "bn_link": None, "dz_link": rl, "res_link": rl}
+        z = vconv(x, convs, None, stats=st)
+        if "part" in st and "part" in raw[1]:
+            return vblock_out(z, raw[0], bns, dsbns, st, raw[1])
+        return vbn(z, bns, stats=st, residual=vbn(raw[0], dsbns, stats=raw[1]), relu=True)
     l1 = {}
     out = cbn(X, [b.conv1 for b in blocks], [b.bn1 for b in blocks], join, link_out=l1, relu=True)
     if hasattr(b0, "conv3"):  # Bottleneck
         l2 = {}
         out = cbn(out, [b.conv2 for b in blocks], [b.bn2 for b in blocks], link_in=l1, link_out=l2, relu=True)
-        return cbn(out, [b.conv3 for b in blocks], [b.bn3 for b in blocks], link_in=l2, residual=idt, relu=True,
-                   residual_join=None if ds else join, res_link=rl)
-    return cbn(out, [b.conv2 for b in blocks], [b.bn2 for b in blocks], link_in=l1, residual=idt, relu=True,
-               residual_join=None if ds else join, res_link=rl)
+        return out_bn(out, [b.conv3 for b in blocks], [b.bn3 for b in blocks], l2)
+    return out_bn(out, [b.conv2 for b in blocks], [b.bn2 for b in blocks], l1)
 
 
 def vlayer(nets, i, X):

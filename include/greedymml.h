@@ -743,6 +743,41 @@ int gm_conv2d_dgrad_grouped_bn_stats_bf16(const gm_conv_desc* d, int G, const vo
 size_t gm_bn_bwd_stats_coef_offset(int C, int G, int rows);
 int gm_bn_bwd_stats_finalize_grouped(const gm_bn_bwd* ps, int G, float* stats, int rows, void* stream);
 int gm_bn_bwd_apply_grouped_bf16(const gm_bn_bwd* ps, int G, const float* stats, int rows, void* stream);
+/* Finalize and apply in one launch.  gm_bn_fwd_finalize_apply_grouped_bf16(ps, G, stats, rows) is
+ * gm_bn_fwd_stats_finalize_grouped followed by gm_bn_fwd_apply_grouped_bf16 on the same arguments,
+ * and gm_bn_bwd_finalize_apply_grouped_bf16 is gm_bn_bwd_stats_finalize_grouped followed by
+ * gm_bn_bwd_apply_grouped_bf16: every output bit (y / dx, mask bytes, statistics, running
+ * statistics, counter, coef_out, coefficient areas, dgamma / dbeta) is the same.  The folded
+ * kernels run gm_bn_fold_blocks(M, C, rows, G) workgroups per (64-channel slice, group); each
+ * combines the slice's partial rows itself (no waiting between workgroups), the first of a slice
+ * alone stores the finalize's outputs, and all stream their share of the slice.  One launch for
+ * any placement of the groups' tensors.  Where gm_bn_fold_blocks returns 0 (the partial rows'
+ * re-read would pass twice the tensor's own bytes, more than 1024 rows, M * C * G > 2^25 elements
+ * over the groups - the bound that declines most 4- and 12-view shapes - or M * C >= 2^31) the two launches are issued instead.
+ * gm_bn_fold_blocks is a pure host function.  The _ex forms take nb: 0 = the rule, > 0 = the
+ * folded kernel with nb workgroups per (slice, group) whatever the rule says (tests, probes). */
+int gm_bn_fold_blocks(long long M, int C, int rows, int G);
+int gm_bn_fwd_finalize_apply_grouped_bf16(const gm_bn_fwd* ps, int G, float* stats, int rows, void* stream);
+int gm_bn_fwd_finalize_apply_grouped_bf16_ex(const gm_bn_fwd* ps, int G, float* stats, int rows, int nb,
+                                             void* stream);
+int gm_bn_bwd_finalize_apply_grouped_bf16(const gm_bn_bwd* ps, int G, float* stats, int rows, void* stream);
+int gm_bn_bwd_finalize_apply_grouped_bf16_ex(const gm_bn_bwd* ps, int G, float* stats, int rows, int nb,
+                                             void* stream);
+/* The residual-affine form, for a block whose residual branch ends in a BatchNorm without ReLU
+ * (the torchvision downsample: conv1x1 -> BatchNorm2d): ps[g].residual is that BatchNorm's RAW
+ * input (the downsample convolution's output), rps[g] its descriptor (x == ps[g].residual, same M
+ * and C, no relu, no residual; y is not written and may be NULL) and rstats / rrows its statistics
+ * buffer as for gm_bn_fwd_stats_finalize_grouped.  Both BatchNorms are finalized (all side outputs
+ * of both, bit for bit) and y = relu?(x*sc + sh + bf16(r*sc_r + sh_r)): the residual rounded to
+ * bf16 exactly as gm_bn_fwd_apply_grouped_bf16 on rps would have stored it, so y and the mask
+ * bytes equal finalize + apply of rps followed by finalize + apply of ps with that tensor as the
+ * residual - without the apply pass and the normalised tensor.  One launch where
+ * gm_bn_fold_blocks(M, C, rows + rrows, G) takes the shape, else two finalizes and one apply. */
+int gm_bn_fwd_finalize_apply_res_affine_grouped_bf16(const gm_bn_fwd* ps, int G, float* stats, int rows,
+                                                     const gm_bn_fwd* rps, float* rstats, int rrows, void* stream);
+int gm_bn_fwd_finalize_apply_res_affine_grouped_bf16_ex(const gm_bn_fwd* ps, int G, float* stats, int rows,
+                                                        const gm_bn_fwd* rps, float* rstats, int rrows, int nb,
+                                                        void* stream);
 int gm_bn_relu_maxpool2d_bwd_grouped_bf16(const gm_pool_desc* d, int G, const void* dy_pool, const void* idx,
                                           const void* xsel, const gm_bn_bwd* ps, void* scratch, size_t scratch_bytes,
                                           void* stream);

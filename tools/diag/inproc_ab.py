@@ -12,6 +12,10 @@ ARMSET: layout      - flat parameter layout: model.grad_order vs reverse registr
                       vs writing it
         ds1x1       - the 1x1 / s2 downsample forwards on k_gemm_ring (gathered A rows) vs k_conv_igemm_ut
         bnchunk     - the single-launch BN backward over view chunks of <= 112 / 56 MB of x + dy vs one launch
+        bn_fold     - the BatchNorm finalize folded into its apply launch where gm_bn_fold_blocks takes the
+                      shape (vtrunk.BN_FOLD) vs always the two launches
+        ds_res_affine - a downsample block's residual BatchNorm applied inside the block-output apply
+                      (vtrunk.DS_RES_AFFINE) vs as a launch of its own
 """
 import os
 import sys
@@ -62,6 +66,18 @@ def arms(name):
             vtrunk.BN_BWD_CHUNK_BYTES = n
         return [("chunk112", lambda: setc(112 << 20)), ("one_launch", lambda: setc(0)),
                 ("chunk56", lambda: setc(56 << 20))]
+    if name == "bn_fold":
+        from greedy_multimodal_learning_amd import vtrunk
+
+        def setf(on):
+            vtrunk.BN_FOLD = on
+        return [("fold", lambda: setf(True)), ("two_launches", lambda: setf(False))]
+    if name == "ds_res_affine":
+        from greedy_multimodal_learning_amd import vtrunk
+
+        def seta(on):
+            vtrunk.DS_RES_AFFINE = on
+        return [("res_affine", lambda: seta(True)), ("own_launch", lambda: seta(False))]
     if name == "ds1x1":
         def setm(m):
             L.check(L.load().gm_conv_set_1x1_gemm(m), "1x1 gemm")
