@@ -72,6 +72,8 @@ EXPORTS = {
                                c_void_p, c_void_p, c_size_t, c_void_p]),
     "gm_group_sumsq_gate": (c_int, [c_void_p, c_int, ctypes.c_longlong, c_int, c_float, c_float,
                                     c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "gm_group_sumsq_sgdm": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_float, c_float,
+                                    c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
 }
 
 _lib = None

@@ -119,6 +119,10 @@ class GroupNorms:
 
     `sums(grad_scale=1.0, lr=0.0)` launches gm_group_sumsq (optionally fused with
     the SGD update) and returns a float64 device tensor [2*ngroups] (no sync).
+    `sums(..., momentum=, weight_decay=, momentum_buffers=)` with a non-zero momentum or
+    weight decay launches gm_group_sumsq_sgdm instead: torch.optim.SGD's update
+    (dampening 0, no Nesterov term) on caller-owned, zero-initialised momentum buffers,
+    with the same sums (the gradient's without the decay term).
     """
 
     def __init__(self, named_params, branchnames, MMTMnames):
@@ -132,6 +136,25 @@ class GroupNorms:
         self._table = None
         self._scratch = None
         self._out = None
+        self._mom_key = None
+        self._mom_table = None
+
+    def _build_mom(self, bufs):
+        """The device array of momentum-buffer pointers (parallel to the parameters; 0 for None)."""
+        if len(bufs) != len(self.params):
+            raise L.GreedyMMLError(f"group norms: {len(bufs)} momentum buffers for {len(self.params)} parameters")
+        key = tuple(0 if b is None else b.data_ptr() for b in bufs)
+        if key == self._mom_key:
+            return
+        for p, b in zip(self.params, bufs):
+            if b is None:
+                if p.grad is not None:
+                    raise L.GreedyMMLError("group norms need a momentum buffer for every parameter with a gradient")
+            elif (b.dtype != torch.float32 or b.device != p.device or not _dense(b) or b.shape != p.shape
+                  or b.stride() != p.stride()):
+                raise L.GreedyMMLError("group norms need dense fp32 gradients laid out like the parameter")
+        self._mom_table = torch.tensor(key, dtype=torch.int64).to(self.device)
+        self._mom_key = key
 
     def _build(self):
         key = tuple((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr()) for p in self.params)
@@ -158,14 +181,30 @@ class GroupNorms:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
             self._out = torch.empty(2 * self.ngroups, dtype=torch.float64, device=self.device)
 
-    def sums(self, grad_scale=1.0, lr=0.0, gate=None, gate_n=False):
+    def sums(self, grad_scale=1.0, lr=0.0, gate=None, gate_n=False, momentum=0.0, weight_decay=0.0,
+             momentum_buffers=None):
         """The step's group sums (and the fused SGD when lr != 0); gate (a device gm_gate_state /
-        gm_gate_state_n tensor): the on-device gate's step runs in the same finalize launch."""
+        gm_gate_state_n tensor): the on-device gate's step runs in the same finalize launch.
+        momentum / weight_decay (either non-zero: gm_group_sumsq_sgdm, whose update runs at
+        any lr): torch.optim.SGD's; momentum_buffers: with a non-zero momentum, a list
+        parallel to the parameters of zero-initialised fp32 tensors shaped and strided like
+        them (None where the parameter has no gradient), advanced in place."""
         L.load()
         if not self.params[0].is_cuda:
             raise L.GreedyMMLError("group norms run on HIP devices only (no CPU fallback)")
         self._build()
         out = torch.empty(2 * self.ngroups, dtype=torch.float64, device=self.device)
+        if momentum != 0 or weight_decay != 0:
+            mom = 0
+            if momentum_buffers is not None:
+                self._build_mom(list(momentum_buffers))
+                mom = self._mom_table.data_ptr()
+            L.check(L.load().gm_group_sumsq_sgdm(
+                self._table.data_ptr(), mom, len(self.params), self.total, self.ngroups, float(grad_scale),
+                float(lr), float(momentum), float(weight_decay), out.data_ptr(), self._scratch.data_ptr(),
+                self._scratch.numel(), L.ptr(gate), int(bool(gate_n)), L.stream_of(self.device)),
+                "gm_group_sumsq_sgdm")
+            return out
         args = (self._table.data_ptr(), len(self.params), self.total, self.ngroups, float(grad_scale), float(lr),
                 out.data_ptr(), self._scratch.data_ptr(), self._scratch.numel())
         if gate is not None:

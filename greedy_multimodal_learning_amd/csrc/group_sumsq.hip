@@ -9,7 +9,10 @@
 // loads, accumulates per-thread fp32 partials per tensor segment, folds them into
 // fp64 per-group sums, and writes one fp64 row per workgroup; a second 1-block
 // pass adds the rows in fixed order.  HBM bytes/step: 8*N (read p, g) without the
-// update, 12*N with it (read p, g; write p).  Deterministic.
+// update, 12*N with it (read p, g; write p), 20*N with a momentum buffer (gm_group_sumsq_sgdm:
+// + read and write b).  Deterministic.
+#include <cmath>
+
 #include "gm_common.h"
 #include "gate_rule.h"
 
@@ -106,6 +109,87 @@ __device__ __forceinline__ void stream_segment(const gm_tensor& T, long long tb,
     }
 }
 
+// ---- momentum / weight-decay form of the update (gm_group_sumsq_sgdm) ----------------
+// torch.optim.SGD(lr, momentum, weight_decay), dampening 0, no Nesterov term, per element:
+//   d = wd*w + g';  b' = mu*b + d;  w' = w - lr*b'      (g' = gscale*g, each line one fma)
+// A zero-initialised buffer gives torch's first step (b' = d) exactly, so there is no step
+// counter.  MOM = false (momentum 0): b' = d stays in registers, no buffer stream.
+struct sgdm_args {
+    float gscale, lr, mu, wd;
+};
+
+template <bool MOM>
+__device__ __forceinline__ float sgdm_update(float w, float g, float& b, const sgdm_args& h) {
+    const float d = fmaf(h.wd, w, g);
+    b = MOM ? fmaf(h.mu, b, d) : d;
+    return fmaf(-h.lr, b, w);
+}
+
+// stream_segment with the update above; mb: the tensor's momentum buffer (MOM only).  The sums
+// take w before the update and g' without the decay term, in stream_segment's order: with mb
+// congruent to p they are bit-identical to its sums.  16-byte path: p, g (and mb) congruent
+// mod 16.  HBM bytes per element: 12 (MOM false), 20 (MOM true: + read and write mb).
+template <bool MOM>
+__device__ __forceinline__ void stream_segment_sgdm(const gm_tensor& T, float* __restrict__ mb, long long tb,
+                                                    long long te, const sgdm_args& h, float& sw, float& sg) {
+    if (T.grad == nullptr || (MOM && mb == nullptr)) {
+        // no gradient: the parameter and its buffer stay as they are (torch: grad is None).  (A
+        // gradient without a buffer is the caller's error; nothing is dereferenced or updated.)
+        stream_segment<false>(T, tb, te, h.gscale, 0.f, sw, sg);
+        return;
+    }
+    float* __restrict__ p = T.param;
+    const float* __restrict__ gr = T.grad;
+    const uintptr_t skew = ((uintptr_t)(p + tb) ^ (uintptr_t)(gr + tb)) |
+                           (MOM ? ((uintptr_t)(p + tb) ^ (uintptr_t)(mb + tb)) : (uintptr_t)0);
+    long long head = tb;
+    if ((skew & 15) == 0) {
+        while (head < te && ((uintptr_t)(p + head) & 15)) ++head;
+    } else {
+        head = te;
+    }
+    auto one = [&](long long i) {
+        const float w = p[i];
+        const float g = gr[i] * h.gscale;
+        sw = fmaf(w, w, sw);
+        sg = fmaf(g, g, sg);
+        float b = MOM ? mb[i] : 0.f;
+        p[i] = sgdm_update<MOM>(w, g, b, h);
+        if (MOM) mb[i] = b;
+    };
+    float4* pv = (float4*)(p + head);
+    const float4* gv = (const float4*)(gr + head);
+    float4* bv = (float4*)(MOM ? mb + head : nullptr);
+    auto four = [&](long long i, const float4 w, float4 g, float4 b) {
+        sw = fmaf(w.x, w.x, sw); sw = fmaf(w.y, w.y, sw);
+        sw = fmaf(w.z, w.z, sw); sw = fmaf(w.w, w.w, sw);
+        g.x *= h.gscale; g.y *= h.gscale; g.z *= h.gscale; g.w *= h.gscale;
+        sg = fmaf(g.x, g.x, sg); sg = fmaf(g.y, g.y, sg);
+        sg = fmaf(g.z, g.z, sg); sg = fmaf(g.w, g.w, sg);
+        pv[i] = make_float4(sgdm_update<MOM>(w.x, g.x, b.x, h), sgdm_update<MOM>(w.y, g.y, b.y, h),
+                            sgdm_update<MOM>(w.z, g.z, b.z, h), sgdm_update<MOM>(w.w, g.w, b.w, h));
+        if (MOM) bv[i] = b;
+    };
+    for (long long i = tb + threadIdx.x; i < head; i += 256) one(i);
+    const long long nv = (te - head) >> 2;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    long long i0 = threadIdx.x;
+    // 4 independent 16-B loads of each stream in flight per thread
+    for (; i0 + 3 * 256 < nv; i0 += 4 * 256) {
+        float4 w[4], g[4], b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            w[u] = pv[i0 + u * 256];
+            g[u] = gv[i0 + u * 256];
+            b[u] = MOM ? bv[i0 + u * 256] : zero4;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) four(i0 + u * 256, w[u], g[u], b[u]);
+    }
+    for (long long i = i0; i < nv; i += 256) four(i, pv[i], gv[i], MOM ? bv[i] : zero4);
+    for (long long i = head + nv * 4 + threadIdx.x; i < te; i += 256) one(i);
+}
+
 template <bool SGD, int MG>
 __global__ __launch_bounds__(256) void k_group_sumsq(const gm_tensor* __restrict__ tab, int nt,
                                                      long long total, int ngroups, float gscale,
@@ -124,6 +208,48 @@ __global__ __launch_bounds__(256) void k_group_sumsq(const gm_tensor* __restrict
         const long long te = min(T.n, e1 - T.offset);            // end (exclusive)
         float sw = 0.f, sg = 0.f;
         stream_segment<SGD>(T, tb, te, gscale, lr, sw, sg);
+        const unsigned m = T.group_mask;
+#pragma unroll
+        for (int g = 0; g < MG; ++g)
+            if (g < ngroups && ((m >> g) & 1u)) { gw[g] += (double)sw; gg[g] += (double)sg; }
+        e = T.offset + te;
+        ++ti;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int g = 0; g < MG; ++g) {
+        if (g >= ngroups) break;
+        const double w = wave_sum_d(gw[g]);
+        const double s = wave_sum_d(gg[g]);
+        if (lane == 0) { sred[wave][2 * g] = w; sred[wave][2 * g + 1] = s; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * ngroups) {
+        const int j = threadIdx.x;
+        rows[(size_t)blockIdx.x * 2 * ngroups + j] = ((sred[0][j] + sred[1][j]) + sred[2][j]) + sred[3][j];
+    }
+}
+
+// k_group_sumsq with the momentum / weight-decay update; mom: the tensors' buffers (MOM only)
+template <bool MOM, int MG>
+__global__ __launch_bounds__(256) void k_group_sumsq_sgdm(const gm_tensor* __restrict__ tab,
+                                                          float* const* __restrict__ mom, int nt, long long total,
+                                                          int ngroups, sgdm_args h, long long chunk,
+                                                          double* __restrict__ rows) {
+    __shared__ double sred[4][2 * MG];
+    const long long e0 = (long long)blockIdx.x * chunk;
+    const long long e1 = min(total, e0 + chunk);
+    double gw[MG], gg[MG];
+#pragma unroll
+    for (int g = 0; g < MG; ++g) { gw[g] = 0.0; gg[g] = 0.0; }
+    int ti = find_tensor(tab, nt, e0);
+    long long e = e0;
+    while (e < e1) {
+        const gm_tensor T = tab[ti];
+        const long long tb = e - T.offset;
+        const long long te = min(T.n, e1 - T.offset);
+        float sw = 0.f, sg = 0.f;
+        stream_segment_sgdm<MOM>(T, MOM ? mom[ti] : nullptr, tb, te, h, sw, sg);
         const unsigned m = T.group_mask;
 #pragma unroll
         for (int g = 0; g < MG; ++g)
@@ -200,6 +326,40 @@ __global__ __launch_bounds__(256) void k_group_sumsq_runs(const gm_tensor* __res
     if (threadIdx.x < 2 * ngroups) rows[(size_t)blockIdx.x * 2 * ngroups + threadIdx.x] = acc[threadIdx.x];
 }
 
+// k_group_sumsq_runs with the momentum / weight-decay update
+template <bool MOM>
+__global__ __launch_bounds__(256) void k_group_sumsq_sgdm_runs(const gm_tensor* __restrict__ tab,
+                                                               float* const* __restrict__ mom, int nt,
+                                                               long long total, int ngroups, sgdm_args h,
+                                                               long long chunk, double* __restrict__ rows) {
+    __shared__ double sred[4][2];
+    __shared__ double acc[2 * kMaxGroups];
+    if (threadIdx.x < 2 * kMaxGroups) acc[threadIdx.x] = 0.0;
+    const long long e0 = (long long)blockIdx.x * chunk;
+    const long long e1 = min(total, e0 + chunk);
+    int ti = find_tensor(tab, nt, e0);
+    unsigned cur = tab[ti].group_mask;
+    double aw = 0.0, ag = 0.0;
+    long long e = e0;
+    while (e < e1) {
+        const gm_tensor T = tab[ti];
+        if (T.group_mask != cur) {
+            flush_run(aw, ag, cur, ngroups, sred, acc);
+            cur = T.group_mask;
+        }
+        const long long tb = e - T.offset;
+        const long long te = min(T.n, e1 - T.offset);
+        float sw = 0.f, sg = 0.f;
+        stream_segment_sgdm<MOM>(T, MOM ? mom[ti] : nullptr, tb, te, h, sw, sg);
+        aw += (double)sw;
+        ag += (double)sg;
+        e = T.offset + te;
+        ++ti;
+    }
+    flush_run(aw, ag, cur, ngroups, sred, acc);
+    if (threadIdx.x < 2 * ngroups) rows[(size_t)blockIdx.x * 2 * ngroups + threadIdx.x] = acc[threadIdx.x];
+}
+
 // 1024 threads stream the [nrows][w] row block as one flat array with fully coalesced
 // 8-byte loads: thread t < S (S = the largest multiple of w <= 1024) owns column t % w and
 // reads elements t, t + S, ... (8 in flight).  The former form gave each thread whole
@@ -265,16 +425,33 @@ extern "C" size_t gm_group_sumsq_scratch(long long total) {
     return (size_t)nb * 2 * kMaxGroups * sizeof(double);
 }
 
-static int group_sumsq(const gm_tensor* table, int nt, long long total, int ngroups, float gscale, float lr,
-                       double* out, void* scratch, size_t scratch_bytes, void* gate, int gate_n, void* stream) {
+// the argument checks every entry point shares
+static int group_sumsq_args(const gm_tensor* table, int nt, long long total, int ngroups, const double* out,
+                            const void* scratch, size_t scratch_bytes) {
     GM_REQUIRE(table && nt >= 1 && total >= 1, "group_sumsq: empty tensor table");
     GM_REQUIRE(ngroups >= 1 && ngroups <= kMaxGroups, "group_sumsq: ngroups must be 1..%d", kMaxGroups);
     GM_REQUIRE(out, "group_sumsq: null output");
     const long long chunk = chunk_elems(total);
-    const long long nb = (total + chunk - 1) / chunk;
-    GM_REQUIRE(nb < (1ll << 31), "group_sumsq: too many elements");
+    GM_REQUIRE((total + chunk - 1) / chunk < (1ll << 31), "group_sumsq: too many elements");
     GM_REQUIRE(scratch && scratch_bytes >= gm_group_sumsq_scratch(total),
                "group_sumsq: scratch %zu < %zu bytes", scratch_bytes, gm_group_sumsq_scratch(total));
+    return 0;
+}
+
+// (main, bypass) groups per branch: 4 for the two-branch gate, 2 nb for the N-branch one (nb in
+// the state: the rule reads 4 nb sums)
+static int gate_groups(int ngroups, int gate_n) {
+    GM_REQUIRE(gate_n ? (ngroups >= 4 && ngroups % 2 == 0) : ngroups == 4,
+               "group_sumsq_gate: %d groups do not match the %s gate", ngroups, gate_n ? "N-branch" : "two-branch");
+    return 0;
+}
+
+static int group_sumsq(const gm_tensor* table, int nt, long long total, int ngroups, float gscale, float lr,
+                       double* out, void* scratch, size_t scratch_bytes, void* gate, int gate_n, void* stream) {
+    int rc0 = group_sumsq_args(table, nt, total, ngroups, out, scratch, scratch_bytes);
+    if (rc0) return rc0;
+    const long long chunk = chunk_elems(total);
+    const long long nb = (total + chunk - 1) / chunk;
     hipStream_t st = as_stream(stream);
     double* rows = (double*)scratch;
     if (ngroups <= 8) {
@@ -303,10 +480,43 @@ extern "C" int gm_group_sumsq_gate(const gm_tensor* table, int nt, long long tot
                                    float lr, double* out, void* scratch, size_t scratch_bytes, void* gate,
                                    int gate_n, void* stream) {
     GM_REQUIRE(gate, "group_sumsq_gate: null gate state");
-    // (main, bypass) groups per branch: 4 for the two-branch gate, 2 nb for the N-branch one (nb in
-    // the state: the rule reads 4 nb sums)
-    GM_REQUIRE(gate_n ? (ngroups >= 4 && ngroups % 2 == 0) : ngroups == 4,
-               "group_sumsq_gate: %d groups do not match the %s gate", ngroups, gate_n ? "N-branch" : "two-branch");
+    int rc = gate_groups(ngroups, gate_n);
+    if (rc) return rc;
     return group_sumsq(table, nt, total, ngroups, gscale, lr, out, scratch, scratch_bytes, gate, gate_n ? 1 : 0,
                        stream);
+}
+
+extern "C" int gm_group_sumsq_sgdm(const gm_tensor* table, float* const* mom, int nt, long long total,
+                                   int ngroups, float gscale, float lr, float momentum, float weight_decay,
+                                   double* out, void* scratch, size_t scratch_bytes, void* gate, int gate_n,
+                                   void* stream) {
+    GM_REQUIRE(std::isfinite(momentum) && momentum >= 0.f, "group_sumsq_sgdm: momentum must be finite and >= 0");
+    GM_REQUIRE(std::isfinite(weight_decay) && weight_decay >= 0.f,
+               "group_sumsq_sgdm: weight_decay must be finite and >= 0");
+    GM_REQUIRE((mom != nullptr) == (momentum != 0.f),
+               "group_sumsq_sgdm: momentum buffers must be given if and only if momentum != 0");
+    int rc = gate ? gate_groups(ngroups, gate_n) : 0;
+    if (rc) return rc;
+    rc = group_sumsq_args(table, nt, total, ngroups, out, scratch, scratch_bytes);
+    if (rc) return rc;
+    const long long chunk = chunk_elems(total);
+    const int nb = (int)((total + chunk - 1) / chunk);
+    hipStream_t st = as_stream(stream);
+    double* rows = (double*)scratch;
+    const sgdm_args h = {gscale, lr, momentum, weight_decay};
+    if (ngroups <= 8) {
+        if (mom)
+            k_group_sumsq_sgdm<true, 8><<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h, chunk, rows);
+        else
+            k_group_sumsq_sgdm<false, 8><<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h, chunk, rows);
+    } else {
+        if (mom)
+            k_group_sumsq_sgdm_runs<true><<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h, chunk, rows);
+        else
+            k_group_sumsq_sgdm_runs<false><<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h, chunk, rows);
+    }
+    rc = check_launch("k_group_sumsq_sgdm");
+    if (rc) return rc;
+    k_group_finalize<<<1, kFinT, 0, st>>>(rows, nb, ngroups, out, gate, gate && gate_n ? 1 : 0);
+    return check_launch("k_group_finalize");
 }

@@ -18,6 +18,8 @@ re-organised for the hardware:
   it, so the sums equal those `compute_BDR` takes before `optimizer.step()`;
   the only host sync per step is the 8-double copy the gate needs for its
   decision (the decision applies to the NEXT forward, as in the reference);
+  with `momentum` / `weight_decay` the same pass applies torch.optim.SGD's rule
+  (`gm_group_sumsq_sgdm`) on a third flat buffer, the momentum buffers;
 * the trunk runs in bf16 (autocast) on channels_last activations; master
   weights, gradients, the MMTM FC chain and all reductions stay fp32;
 * `graphs=True`: after one eager step, each curation setting
@@ -261,9 +263,16 @@ class BalancedStep:
     def __init__(self, model, lr=0.1, gate=None, compute_dtype=torch.bfloat16, channels_last=True,
                  process_group=None, bucket_mb=25.0, branchnames=("net_view_0", "net_view_1"),
                  MMTMnames=("visual", "skeleton"), graphs=False, device_gate=None, dp_buckets=None,
-                 mmtm_excite=None, f32_contraction=None):
+                 mmtm_excite=None, f32_contraction=None, momentum=0.0, weight_decay=0.0):
+        import math
         self.model = model
         self.lr = float(lr)
+        # torch.optim.SGD's momentum and weight decay (dampening 0, no Nesterov term), fixed per
+        # engine; both 0 (the default): the plain update, no momentum buffer
+        self.momentum, self.weight_decay = float(momentum), float(weight_decay)
+        for name, v in (("momentum", self.momentum), ("weight_decay", self.weight_decay)):
+            if not (math.isfinite(v) and v >= 0.0):
+                raise ValueError(f"BalancedStep: {name} must be finite and >= 0 (got {v!r})")
         self.gate = gate
         self.compute_dtype = compute_dtype
         # f32_contraction (None / "exact" / "bf16x3" / "bf16x6"): how the fp32 trunk's
@@ -295,6 +304,14 @@ class BalancedStep:
             from . import vtrunk
             vtrunk._wgrad_stream(self.device)  # (the stacked trunk's weight-gradient stream, likewise)
         self.norms = GroupNorms(named, list(branchnames), list(MMTMnames))
+        # one flat zero momentum buffer at FlatParams' offsets (so co-aligned with the parameter
+        # and gradient buffers: the fused pass keeps its 16-byte path), made here, before any
+        # capture: the graph mutates it in place
+        self.flat_momentum = None
+        self._mom_bufs = None
+        if self.momentum != 0.0:
+            self.flat_momentum = torch.zeros(self.flat.total, device=self.device, dtype=torch.float32)
+            self._mom_bufs = [self.momentum_buffer(p) for _, p in named]
         if gate is not None:
             gate.set_model(model, ignore=False)
             gate.set_model_pytoune(self.flags)
@@ -437,10 +454,26 @@ class BalancedStep:
     def _sums_and_gate(self):
         """The fused norms+SGD pass; with the on-device gate its step rides in the same finalize
         launch (gm_group_sumsq_gate)."""
+        kw = {}
+        if self.momentum != 0.0 or self.weight_decay != 0.0:  # gm_group_sumsq_sgdm
+            kw = dict(momentum=self.momentum, weight_decay=self.weight_decay, momentum_buffers=self._mom_bufs)
         if self.device_gate:
             return self.norms.sums(grad_scale=1.0 / self.world, lr=self.lr, gate=self.gate_state,
-                                   gate_n=self.gate_n)
-        return self.norms.sums(grad_scale=1.0 / self.world, lr=self.lr)
+                                   gate_n=self.gate_n, **kw)
+        return self.norms.sums(grad_scale=1.0 / self.world, lr=self.lr, **kw)
+
+    def momentum_buffer(self, p):
+        """The momentum buffer of parameter p: a view of the flat buffer shaped and strided like
+        p (a channels-last conv weight's is the same permuted view as p.data); None with
+        momentum 0."""
+        if self.flat_momentum is None:
+            return None
+        off, n = self.flat.slices[p]
+        view = self.flat_momentum[off:off + n]
+        if p.dim() == 4 and self.channels_last:
+            O, I, kh, kw = p.shape
+            return view.view(O, kh, kw, I).permute(0, 3, 1, 2)
+        return view.view(p.shape)
 
     def gate_struct(self):
         """The device gate state as its ctypes mirror (GateState / GateStateN); a host sync."""

@@ -183,13 +183,17 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
                   valid=None, test=None, test_steps=None, validation_steps=None, use_gpu=True, device_numbers=[0],
                   custom_callbacks=[], checkpoint_monitor="val_acc", n_epochs=100, verbose=True, nummodalities=2,
                   compute_dtype="fp32", graphs=True, f32_contraction="exact", eval_engine="modules",
-                  eval_f32_trunk="modules"):
+                  eval_f32_trunk="modules", fused_momentum=False):
     """Reference src/training_loop.py:86-143 + Model_.train_loop (src/framework.py:
     250-330) on the fused engine.  `optimizer` is the (lr, momentum, wd) triple of the
-    reference's SGD (only momentum = wd = 0, as every config uses, is fused; a torch SGD
-    over the model's parameters holds the learning rate and the state_dict the
-    checkpoints carry, and ReduceLROnPlateau_PyTorch drives it); `metrics` and
-    `loss_function` are the reference's acc / blend_loss (fixed in the engine).
+    reference's SGD (a torch SGD over the model's parameters holds the learning rate and
+    the state_dict the checkpoints carry, and ReduceLROnPlateau_PyTorch drives it; it is
+    never stepped).  By default only momentum = wd = 0, as every reference config uses, is
+    accepted; `fused_momentum=True` (gin: `training_loop.fused_momentum=True`) hands a
+    non-zero momentum / weight decay to the engine's fused pass (torch.optim.SGD's rule,
+    dampening 0, no Nesterov term), and each checkpoint's 'optimizer' entry then carries
+    the engine's momentum buffers as `momentum_buffer` state, as the reference's would.
+    `metrics` and `loss_function` are the reference's acc / blend_loss (fixed in the engine).
     Epochs 1 .. n_epochs-1 as the reference (`epochs=n_epochs - 1`).  Per epoch the
     history gets the reference's train_dict keys (`loss`, `acc`, `acc_modal_{i}`,
     `train_indices`), the validation / test dicts, and the gate's per-step lists; a NaN
@@ -203,9 +207,10 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
 
     from .engine import BalancedStep
     lr, momentum, wd = optimizer
-    if momentum != 0 or wd != 0:
-        raise NotImplementedError("the fused step implements SGD with momentum = weight_decay = 0 "
-                                  "(train.momentum / train.wd of every reference config)")
+    if (momentum != 0 or wd != 0) and not fused_momentum:
+        raise NotImplementedError("by default the fused step implements SGD with momentum = weight_decay = 0 "
+                                  "(train.momentum / train.wd of every reference config); bind "
+                                  "training_loop.fused_momentum=True for the fused momentum / weight-decay update")
     dev = torch.device("cuda", device_numbers[0])
     model = model.to(dev)
     gates = [c for c in custom_callbacks if hasattr(c, "on_backward_end")
@@ -215,7 +220,8 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
     gate = gates[0] if gates else None
     cdt = _DTYPES[compute_dtype]
     step = BalancedStep(model, lr=lr, gate=gate, compute_dtype=cdt, channels_last=True, graphs=graphs,
-                        f32_contraction=f32_contraction_arg(cdt, f32_contraction))
+                        f32_contraction=f32_contraction_arg(cdt, f32_contraction), momentum=momentum,
+                        weight_decay=wd)
     # the reference's optimizer object (never stepped: the engine's fused pass applies the
     # update with the learning rate read from it)
     opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=wd)
@@ -309,6 +315,9 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
             c.on_epoch_end(epoch, logs)
         if save_path:
             save_history(H, save_path)
+            if step.flat_momentum is not None:  # what the reference's stepped SGD would hold
+                for p in model.parameters():
+                    opt.state[p]["momentum_buffer"] = step.momentum_buffer(p).detach().clone()
             ck = {"model": model.state_dict(), "optimizer": opt.state_dict()}
             mon = logs.get(checkpoint_monitor)
             if mon is not None and (best is None or mon > best):

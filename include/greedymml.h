@@ -223,7 +223,8 @@ int gm_mmtm_running_avg_dev(const float* e_v, int ld_e, int B, int C, float* ra_
  * Per-branch weight / gradient norms for the conditional-learning-speed gate
  * (Bias_Mitigation_Strong.compute_BDR, src/callbacks.py:199-233), optionally fused
  * with the SGD update of the same parameters (torch.optim.SGD momentum=0, wd=0;
- * train.py:48-51, src/framework.py:315):
+ * train.py:48-51, src/framework.py:315; gm_group_sumsq_sgdm below: with momentum and
+ * weight decay):
  *   out[2*g]   = sum over tensors with bit g in group_mask of sum(param^2)
  *   out[2*g+1] = same for sum((grad*grad_scale)^2)
  *   if lr != 0: param -= lr * grad * grad_scale   (after reading param)
@@ -354,6 +355,27 @@ int gm_group_sumsq(const gm_tensor* table, int ntensors, long long total_elems, 
  * identical sums and state to the two calls */
 int gm_group_sumsq_gate(const gm_tensor* table, int nt, long long total, int ngroups, float gscale, float lr,
                         double* out, void* scratch, size_t scratch_bytes, void* gate, int gate_n, void* stream);
+/* The same pass with torch.optim.SGD's momentum and weight decay (dampening 0, no Nesterov
+ * term; reference train.py:43-51).  Per element, g' = grad * grad_scale, each line one fused
+ * multiply-add:
+ *     d  = weight_decay * w + g'
+ *     b' = momentum * b + d          (b: the tensor's momentum buffer)
+ *     w' = w - lr * b'
+ * The caller zero-initialises the buffers, which makes torch's first step (b' = d) exact
+ * without a step counter.  The sums are the ones gm_group_sumsq returns: w before the update,
+ * g' WITHOUT the decay term (compute_BDR reads p.grad before optimizer.step()); with buffers
+ * congruent to their parameters mod 16 bytes they are bit-identical to gm_group_sumsq's.
+ * mom: DEVICE array of ntensors buffer pointers (each as long as its tensor), NULL if and only
+ * if momentum == 0 (then b' = d stays in registers: 12 bytes per element; otherwise 20).
+ * A table entry whose grad is NULL is skipped: parameter and buffer untouched; its mom entry may
+ * be NULL.  A zero gradient still decays the parameter and moves it by its momentum.  The update
+ * always runs (lr == 0: the buffers advance, the parameters stay).  momentum and weight_decay
+ * must be finite and >= 0.  Scratch as gm_group_sumsq; gate NULL: no gate, else as
+ * gm_group_sumsq_gate (same group-count rule, same finalize launch). */
+int gm_group_sumsq_sgdm(const gm_tensor* table, float* const* mom, int ntensors, long long total,
+                        int ngroups, float grad_scale, float lr, float momentum, float weight_decay,
+                        double* out, void* scratch, size_t scratch_bytes, void* gate, int gate_n,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------
  * ResNet trunk convolutions (torchvision resnet18/50 Conv2d, bias=False; called

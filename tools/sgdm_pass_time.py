@@ -1,0 +1,79 @@
+"""Time the norms+update pass in its three forms at the C2 parameter set (MMTM_MVCNN, 2 views:
+23,773,008 elements in the engine's flat buffers): the plain update (gm_group_sumsq, 12 B per
+element), weight decay alone (gm_group_sumsq_sgdm without buffers, 12 B) and momentum + weight
+decay (20 B).  One process, the forms interleaved launch by launch within a round, HIP events
+around each launch pair (pass + finalize) behind a device sleep, as bench.time_group_sumsq does;
+prints one JSON line: per form the median over rounds of the round's mean, the spread over the
+rounds, and the achieved bytes/s against the 8.0 TB/s HBM3E peak.
+
+    python tools/sgdm_pass_time.py [--rounds 7] [--launches 20] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+HBM_PEAK = 8.0e12  # bytes/s
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    from greedy_multimodal_learning_amd.engine import BalancedStep
+    from greedy_multimodal_learning_amd.model import MMTM_MVCNN
+    if not torch.cuda.is_available():
+        raise SystemExit("sgdm_pass_time: needs a HIP device (no CPU timing)")
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    st = BalancedStep(MMTM_MVCNN().to(dev), lr=1e-4, momentum=0.9, weight_decay=5e-4)
+    st.flat.grad.normal_(generator=torch.Generator(device=dev).manual_seed(1)).mul_(1e-3)
+    n = st.flat.total
+    forms = {
+        "plain": (12, dict()),
+        "weight_decay": (12, dict(weight_decay=5e-4)),
+        "momentum": (20, dict(momentum=0.9, weight_decay=5e-4, momentum_buffers=st._mom_bufs)),
+    }
+    stream = torch.cuda.current_stream()
+    for _, kw in forms.values():  # warm up every form
+        for _ in range(3):
+            st.norms.sums(lr=st.lr, **kw)
+    means = {k: [] for k in forms}
+    for _ in range(a.rounds):
+        torch.cuda.synchronize()
+        torch.cuda._sleep(50_000_000)
+        evs = {k: [] for k in forms}
+        for _ in range(a.launches):
+            for k, (_, kw) in forms.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                st.norms.sums(lr=st.lr, **kw)
+                e1.record(stream)
+                evs[k].append((e0, e1))
+        torch.cuda.synchronize()
+        for k in forms:
+            means[k].append(sum(x.elapsed_time(y) for x, y in evs[k]) / a.launches * 1e3)  # us
+    res = {"elements": n, "rounds": a.rounds, "launches_per_round": a.launches}
+    for k, (bpe, _) in forms.items():
+        med = statistics.median(means[k])
+        res[k] = {"us": round(med, 2), "spread_us": round(max(means[k]) - min(means[k]), 2),
+                  "bytes": bpe * n, "tb_per_s": round(bpe * n / (med * 1e-6) / 1e12, 3),
+                  "hbm_peak_fraction": round(bpe * n / (med * 1e-6) / HBM_PEAK, 3)}
+    res["momentum_over_plain"] = round(res["momentum"]["us"] / res["plain"]["us"], 3)
+    assert torch.isfinite(st.flat.param).all() and torch.isfinite(st.flat_momentum).all()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
