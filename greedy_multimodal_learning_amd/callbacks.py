@@ -194,24 +194,25 @@ class GroupNorms:
             raise L.GreedyMMLError("group norms run on HIP devices only (no CPU fallback)")
         self._build()
         out = torch.empty(2 * self.ngroups, dtype=torch.float64, device=self.device)
-        if momentum != 0 or weight_decay != 0:
-            mom = 0
-            if momentum_buffers is not None:
-                self._build_mom(list(momentum_buffers))
-                mom = self._mom_table.data_ptr()
-            L.check(L.load().gm_group_sumsq_sgdm(
-                self._table.data_ptr(), mom, len(self.params), self.total, self.ngroups, float(grad_scale),
-                float(lr), float(momentum), float(weight_decay), out.data_ptr(), self._scratch.data_ptr(),
-                self._scratch.numel(), L.ptr(gate), int(bool(gate_n)), L.stream_of(self.device)),
-                "gm_group_sumsq_sgdm")
-            return out
-        args = (self._table.data_ptr(), len(self.params), self.total, self.ngroups, float(grad_scale), float(lr),
-                out.data_ptr(), self._scratch.data_ptr(), self._scratch.numel())
-        if gate is not None:
-            L.check(L.load().gm_group_sumsq_gate(*args, gate.data_ptr(), int(bool(gate_n)),
-                                                 L.stream_of(self.device)), "gm_group_sumsq_gate")
+        sgdm = momentum != 0 or weight_decay != 0
+        mom = 0
+        if sgdm and momentum_buffers is not None:
+            self._build_mom(list(momentum_buffers))
+            mom = self._mom_table.data_ptr()
+        lib, table, stream = L.load(), self._table.data_ptr(), L.stream_of(self.device)
+        sizes = (len(self.params), self.total, self.ngroups, float(grad_scale), float(lr))
+        bufs = (out.data_ptr(), self._scratch.data_ptr(), self._scratch.numel())
+        if sgdm:
+            name = "gm_group_sumsq_sgdm"
+            rc = lib.gm_group_sumsq_sgdm(table, mom, *sizes, float(momentum), float(weight_decay), *bufs,
+                                         L.ptr(gate), int(bool(gate_n)), stream)
+        elif gate is not None:
+            name = "gm_group_sumsq_gate"
+            rc = lib.gm_group_sumsq_gate(table, *sizes, *bufs, gate.data_ptr(), int(bool(gate_n)), stream)
         else:
-            L.check(L.load().gm_group_sumsq(*args, L.stream_of(self.device)), "gm_group_sumsq")
+            name = "gm_group_sumsq"
+            rc = lib.gm_group_sumsq(table, *sizes, *bufs, stream)
+        L.check(rc, name)
         return out
 
 

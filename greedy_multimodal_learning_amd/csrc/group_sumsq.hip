@@ -11,6 +11,12 @@
 // pass adds the rows in fixed order.  HBM bytes/step: 8*N (read p, g) without the
 // update, 12*N with it (read p, g; write p), 20*N with a momentum buffer (gm_group_sumsq_sgdm:
 // + read and write b).  Deterministic.
+//
+// One of each: the update rule (sgd_update<upd>), the streaming loops and sums
+// (stream_segment<upd>), the chunk body per group-count form (chunk_sums, chunk_sums_runs) and
+// the host launch path (group_sumsq).  The update form - none, sgd, decay, mom - is a template
+// parameter all the way down; the eight __global__ kernels and the three entry points are
+// wrappers that choose it.
 #include <cmath>
 
 #include "gm_common.h"
@@ -40,108 +46,50 @@ __device__ __forceinline__ int find_tensor(const gm_tensor* t, int nt, long long
     return lo;
 }
 
-// Streams elements [tb, te) of one tensor: accumulates w^2 and (gscale*g)^2 into sw, sg
-// and applies the SGD update in place.
-template <bool SGD>
-__device__ __forceinline__ void stream_segment(const gm_tensor& T, long long tb, long long te,
-                                               float gscale, float lr, float& sw, float& sg) {
-    float* __restrict__ p = T.param;
-    const float* __restrict__ gr = T.grad;
-    // scalar head up to 16-byte alignment of p (and g)
-    long long a = tb;
-    const bool vec_ok = gr == nullptr || (((uintptr_t)(p + a) ^ (uintptr_t)(gr + a)) & 15) == 0;
-    long long head = a;
-    if (vec_ok) {
-        while (head < te && ((uintptr_t)(p + head) & 15)) ++head;
-    } else {
-        head = te;
-    }
-    for (long long i = a + threadIdx.x; i < head; i += 256) {
-        const float w = p[i];
-        const float g = gr ? gr[i] * gscale : 0.f;
-        sw = fmaf(w, w, sw);
-        sg = fmaf(g, g, sg);
-        if (SGD && gr) p[i] = fmaf(-lr, g, w);
-    }
-    const long long nv = (te - head) >> 2;
-    float4* pv = (float4*)(p + head);
-    const float4* gv = (const float4*)(gr ? gr + head : nullptr);
-    long long i0 = threadIdx.x;
-    if (gr) {
-        // 4 independent 16-B loads of each stream in flight per thread
-        for (; i0 + 3 * 256 < nv; i0 += 4 * 256) {
-            float4 w[4], g[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { w[u] = pv[i0 + u * 256]; g[u] = gv[i0 + u * 256]; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                sw = fmaf(w[u].x, w[u].x, sw); sw = fmaf(w[u].y, w[u].y, sw);
-                sw = fmaf(w[u].z, w[u].z, sw); sw = fmaf(w[u].w, w[u].w, sw);
-                g[u].x *= gscale; g[u].y *= gscale; g[u].z *= gscale; g[u].w *= gscale;
-                sg = fmaf(g[u].x, g[u].x, sg); sg = fmaf(g[u].y, g[u].y, sg);
-                sg = fmaf(g[u].z, g[u].z, sg); sg = fmaf(g[u].w, g[u].w, sg);
-                if (SGD)
-                    pv[i0 + u * 256] = make_float4(fmaf(-lr, g[u].x, w[u].x), fmaf(-lr, g[u].y, w[u].y),
-                                                   fmaf(-lr, g[u].z, w[u].z), fmaf(-lr, g[u].w, w[u].w));
-            }
-        }
-    }
-    for (long long i = i0; i < nv; i += 256) {
-        const float4 w = pv[i];
-        sw = fmaf(w.x, w.x, sw); sw = fmaf(w.y, w.y, sw);
-        sw = fmaf(w.z, w.z, sw); sw = fmaf(w.w, w.w, sw);
-        if (gr) {
-            float4 g = gv[i];
-            g.x *= gscale; g.y *= gscale; g.z *= gscale; g.w *= gscale;
-            sg = fmaf(g.x, g.x, sg); sg = fmaf(g.y, g.y, sg);
-            sg = fmaf(g.z, g.z, sg); sg = fmaf(g.w, g.w, sg);
-            if (SGD)
-                pv[i] = make_float4(fmaf(-lr, g.x, w.x), fmaf(-lr, g.y, w.y),
-                                    fmaf(-lr, g.z, w.z), fmaf(-lr, g.w, w.w));
-        }
-    }
-    for (long long i = head + nv * 4 + threadIdx.x; i < te; i += 256) {
-        const float w = p[i];
-        const float g = gr ? gr[i] * gscale : 0.f;
-        sw = fmaf(w, w, sw);
-        sg = fmaf(g, g, sg);
-        if (SGD && gr) p[i] = fmaf(-lr, g, w);
-    }
-}
-
-// ---- momentum / weight-decay form of the update (gm_group_sumsq_sgdm) ----------------
-// torch.optim.SGD(lr, momentum, weight_decay), dampening 0, no Nesterov term, per element:
-//   d = wd*w + g';  b' = mu*b + d;  w' = w - lr*b'      (g' = gscale*g, each line one fma)
+// ---- the update: torch.optim.SGD(lr, momentum, weight_decay), dampening 0, no Nesterov term ----
+// Per element, with g' = gscale*g and each line one fma:
+//   d = wd*w + g';  b' = mu*b + d;  w' = w - lr*b'
 // A zero-initialised buffer gives torch's first step (b' = d) exactly, so there is no step
-// counter.  MOM = false (momentum 0): b' = d stays in registers, no buffer stream.
+// counter.  The form is a compile-time choice: decay keeps b' = d in registers (no buffer
+// stream), sgd is d = g' as well (w' = w - lr*g'), none writes nothing.
+enum class upd { none, sgd, decay, mom };
+
 struct sgdm_args {
     float gscale, lr, mu, wd;
 };
 
-template <bool MOM>
-__device__ __forceinline__ float sgdm_update(float w, float g, float& b, const sgdm_args& h) {
+template <upd U>
+__device__ __forceinline__ float sgd_update(float w, float g, float& b, const sgdm_args& h) {
+    if (U == upd::sgd) return fmaf(-h.lr, g, w);
     const float d = fmaf(h.wd, w, g);
-    b = MOM ? fmaf(h.mu, b, d) : d;
+    b = U == upd::mom ? fmaf(h.mu, b, d) : d;
     return fmaf(-h.lr, b, w);
 }
 
-// stream_segment with the update above; mb: the tensor's momentum buffer (MOM only).  The sums
-// take w before the update and g' without the decay term, in stream_segment's order: with mb
-// congruent to p they are bit-identical to its sums.  16-byte path: p, g (and mb) congruent
-// mod 16.  HBM bytes per element: 12 (MOM false), 20 (MOM true: + read and write mb).
-template <bool MOM>
-__device__ __forceinline__ void stream_segment_sgdm(const gm_tensor& T, float* __restrict__ mb, long long tb,
-                                                    long long te, const sgdm_args& h, float& sw, float& sg) {
-    if (T.grad == nullptr || (MOM && mb == nullptr)) {
-        // no gradient: the parameter and its buffer stay as they are (torch: grad is None).  (A
-        // gradient without a buffer is the caller's error; nothing is dereferenced or updated.)
-        stream_segment<false>(T, tb, te, h.gscale, 0.f, sw, sg);
+// Streams elements [tb, te) of one tensor: accumulates w^2 and g'^2 into sw, sg and applies the
+// update in place; mb: the tensor's momentum buffer (upd::mom only).  The sums take w before the
+// update and g' without the decay term, in one order for every form: they are bit-identical
+// between the forms.  16-byte path: p, g (and mb) congruent mod 16, else the scalar loop.  HBM
+// bytes per element: 8 (none), 12 (sgd, decay), 20 (mom: + read and write mb).
+// An entry without a gradient is summed for w^2 only and not written (torch: grad is None).  The
+// sgd form tests for it inline; decay and mom hand it to the sums-only form up front, and so know
+// the gradient present below at compile time (inline it costs upd::mom 5 VGPRs and a wave per
+// SIMD).  mom also hands over a gradient without a buffer (the caller's error): nothing of it is
+// dereferenced or updated.
+template <upd U>
+__device__ __forceinline__ void stream_segment(const gm_tensor& T, float* __restrict__ mb, long long tb,
+                                               long long te, const sgdm_args& h, float& sw, float& sg) {
+    constexpr bool MOM = U == upd::mom, EARLY = U == upd::decay || U == upd::mom;
+    if (EARLY && (T.grad == nullptr || (MOM && mb == nullptr))) {
+        stream_segment<upd::none>(T, nullptr, tb, te, h, sw, sg);
         return;
     }
     float* __restrict__ p = T.param;
     const float* __restrict__ gr = T.grad;
-    const uintptr_t skew = ((uintptr_t)(p + tb) ^ (uintptr_t)(gr + tb)) |
-                           (MOM ? ((uintptr_t)(p + tb) ^ (uintptr_t)(mb + tb)) : (uintptr_t)0);
+    const bool hg = EARLY || gr != nullptr;
+    const uintptr_t skew = (hg ? (uintptr_t)(p + tb) ^ (uintptr_t)(gr + tb) : (uintptr_t)0) |
+                           (MOM ? (uintptr_t)(p + tb) ^ (uintptr_t)(mb + tb) : (uintptr_t)0);
+    // scalar head up to 16-byte alignment of p (and g, mb)
     long long head = tb;
     if ((skew & 15) == 0) {
         while (head < te && ((uintptr_t)(p + head) & 15)) ++head;
@@ -150,50 +98,66 @@ __device__ __forceinline__ void stream_segment_sgdm(const gm_tensor& T, float* _
     }
     auto one = [&](long long i) {
         const float w = p[i];
-        const float g = gr[i] * h.gscale;
+        const float g = hg ? gr[i] * h.gscale : 0.f;
         sw = fmaf(w, w, sw);
         sg = fmaf(g, g, sg);
-        float b = MOM ? mb[i] : 0.f;
-        p[i] = sgdm_update<MOM>(w, g, b, h);
-        if (MOM) mb[i] = b;
+        if (U != upd::none && hg) {
+            float b = MOM ? mb[i] : 0.f;
+            p[i] = sgd_update<U>(w, g, b, h);
+            if (MOM) mb[i] = b;
+        }
     };
     float4* pv = (float4*)(p + head);
-    const float4* gv = (const float4*)(gr + head);
+    const float4* gv = (const float4*)(hg ? gr + head : nullptr);
     float4* bv = (float4*)(MOM ? mb + head : nullptr);
-    auto four = [&](long long i, const float4 w, float4 g, float4 b) {
+    auto sumw4 = [&](const float4 w) {
         sw = fmaf(w.x, w.x, sw); sw = fmaf(w.y, w.y, sw);
         sw = fmaf(w.z, w.z, sw); sw = fmaf(w.w, w.w, sw);
+    };
+    auto grad4 = [&](long long i, const float4 w, float4 g, float4 b) {
         g.x *= h.gscale; g.y *= h.gscale; g.z *= h.gscale; g.w *= h.gscale;
         sg = fmaf(g.x, g.x, sg); sg = fmaf(g.y, g.y, sg);
         sg = fmaf(g.z, g.z, sg); sg = fmaf(g.w, g.w, sg);
-        pv[i] = make_float4(sgdm_update<MOM>(w.x, g.x, b.x, h), sgdm_update<MOM>(w.y, g.y, b.y, h),
-                            sgdm_update<MOM>(w.z, g.z, b.z, h), sgdm_update<MOM>(w.w, g.w, b.w, h));
+        if (U != upd::none)
+            pv[i] = make_float4(sgd_update<U>(w.x, g.x, b.x, h), sgd_update<U>(w.y, g.y, b.y, h),
+                                sgd_update<U>(w.z, g.z, b.z, h), sgd_update<U>(w.w, g.w, b.w, h));
         if (MOM) bv[i] = b;
     };
     for (long long i = tb + threadIdx.x; i < head; i += 256) one(i);
     const long long nv = (te - head) >> 2;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     long long i0 = threadIdx.x;
-    // 4 independent 16-B loads of each stream in flight per thread
-    for (; i0 + 3 * 256 < nv; i0 += 4 * 256) {
-        float4 w[4], g[4], b[4];
+    if (hg) {
+        // 4 independent 16-B loads of each stream in flight per thread
+        for (; i0 + 3 * 256 < nv; i0 += 4 * 256) {
+            float4 w[4], g[4], b[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            w[u] = pv[i0 + u * 256];
-            g[u] = gv[i0 + u * 256];
-            b[u] = MOM ? bv[i0 + u * 256] : zero4;
+            for (int u = 0; u < 4; ++u) {
+                w[u] = pv[i0 + u * 256];
+                g[u] = gv[i0 + u * 256];
+                b[u] = MOM ? bv[i0 + u * 256] : zero4;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                sumw4(w[u]);
+                grad4(i0 + u * 256, w[u], g[u], b[u]);
+            }
         }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) four(i0 + u * 256, w[u], g[u], b[u]);
     }
-    for (long long i = i0; i < nv; i += 256) four(i, pv[i], gv[i], MOM ? bv[i] : zero4);
+    for (long long i = i0; i < nv; i += 256) {
+        const float4 w = pv[i];
+        sumw4(w);
+        if (hg) grad4(i, w, gv[i], MOM ? bv[i] : zero4);
+    }
     for (long long i = head + nv * 4 + threadIdx.x; i < te; i += 256) one(i);
 }
 
-template <bool SGD, int MG>
-__global__ __launch_bounds__(256) void k_group_sumsq(const gm_tensor* __restrict__ tab, int nt,
-                                                     long long total, int ngroups, float gscale,
-                                                     float lr, long long chunk, double* __restrict__ rows) {
+// One workgroup's chunk, <= 8 groups: per-thread fp64 sums per group, folded over the waves in
+// fixed order into one row.  mom: the tensors' buffers (upd::mom only)
+template <upd U, int MG>
+__device__ __forceinline__ void chunk_sums(const gm_tensor* __restrict__ tab, float* const* __restrict__ mom,
+                                           int nt, long long total, int ngroups, const sgdm_args& h,
+                                           long long chunk, double* __restrict__ rows) {
     __shared__ double sred[4][2 * MG];
     const long long e0 = (long long)blockIdx.x * chunk;
     const long long e1 = min(total, e0 + chunk);
@@ -207,49 +171,7 @@ __global__ __launch_bounds__(256) void k_group_sumsq(const gm_tensor* __restrict
         const long long tb = e - T.offset;                       // first local element
         const long long te = min(T.n, e1 - T.offset);            // end (exclusive)
         float sw = 0.f, sg = 0.f;
-        stream_segment<SGD>(T, tb, te, gscale, lr, sw, sg);
-        const unsigned m = T.group_mask;
-#pragma unroll
-        for (int g = 0; g < MG; ++g)
-            if (g < ngroups && ((m >> g) & 1u)) { gw[g] += (double)sw; gg[g] += (double)sg; }
-        e = T.offset + te;
-        ++ti;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int g = 0; g < MG; ++g) {
-        if (g >= ngroups) break;
-        const double w = wave_sum_d(gw[g]);
-        const double s = wave_sum_d(gg[g]);
-        if (lane == 0) { sred[wave][2 * g] = w; sred[wave][2 * g + 1] = s; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * ngroups) {
-        const int j = threadIdx.x;
-        rows[(size_t)blockIdx.x * 2 * ngroups + j] = ((sred[0][j] + sred[1][j]) + sred[2][j]) + sred[3][j];
-    }
-}
-
-// k_group_sumsq with the momentum / weight-decay update; mom: the tensors' buffers (MOM only)
-template <bool MOM, int MG>
-__global__ __launch_bounds__(256) void k_group_sumsq_sgdm(const gm_tensor* __restrict__ tab,
-                                                          float* const* __restrict__ mom, int nt, long long total,
-                                                          int ngroups, sgdm_args h, long long chunk,
-                                                          double* __restrict__ rows) {
-    __shared__ double sred[4][2 * MG];
-    const long long e0 = (long long)blockIdx.x * chunk;
-    const long long e1 = min(total, e0 + chunk);
-    double gw[MG], gg[MG];
-#pragma unroll
-    for (int g = 0; g < MG; ++g) { gw[g] = 0.0; gg[g] = 0.0; }
-    int ti = find_tensor(tab, nt, e0);
-    long long e = e0;
-    while (e < e1) {
-        const gm_tensor T = tab[ti];
-        const long long tb = e - T.offset;
-        const long long te = min(T.n, e1 - T.offset);
-        float sw = 0.f, sg = 0.f;
-        stream_segment_sgdm<MOM>(T, MOM ? mom[ti] : nullptr, tb, te, h, sw, sg);
+        stream_segment<U>(T, U == upd::mom ? mom[ti] : nullptr, tb, te, h, sw, sg);
         const unsigned m = T.group_mask;
 #pragma unroll
         for (int g = 0; g < MG; ++g)
@@ -294,10 +216,10 @@ __device__ __forceinline__ void flush_run(double& aw, double& ag, unsigned mask,
     ag = 0.0;
 }
 
-template <bool SGD>
-__global__ __launch_bounds__(256) void k_group_sumsq_runs(const gm_tensor* __restrict__ tab, int nt,
-                                                          long long total, int ngroups, float gscale,
-                                                          float lr, long long chunk, double* __restrict__ rows) {
+template <upd U>
+__device__ __forceinline__ void chunk_sums_runs(const gm_tensor* __restrict__ tab, float* const* __restrict__ mom,
+                                                int nt, long long total, int ngroups, const sgdm_args& h,
+                                                long long chunk, double* __restrict__ rows) {
     __shared__ double sred[4][2];
     __shared__ double acc[2 * kMaxGroups];
     if (threadIdx.x < 2 * kMaxGroups) acc[threadIdx.x] = 0.0;
@@ -316,7 +238,7 @@ __global__ __launch_bounds__(256) void k_group_sumsq_runs(const gm_tensor* __res
         const long long tb = e - T.offset;
         const long long te = min(T.n, e1 - T.offset);
         float sw = 0.f, sg = 0.f;
-        stream_segment<SGD>(T, tb, te, gscale, lr, sw, sg);
+        stream_segment<U>(T, U == upd::mom ? mom[ti] : nullptr, tb, te, h, sw, sg);
         aw += (double)sw;
         ag += (double)sg;
         e = T.offset + te;
@@ -326,38 +248,36 @@ __global__ __launch_bounds__(256) void k_group_sumsq_runs(const gm_tensor* __res
     if (threadIdx.x < 2 * ngroups) rows[(size_t)blockIdx.x * 2 * ngroups + threadIdx.x] = acc[threadIdx.x];
 }
 
-// k_group_sumsq_runs with the momentum / weight-decay update
+// The kernels: the two bodies above per update form.  The plain pair (gm_group_sumsq, _gate) keeps
+// its name and argument layout: profiles and tools find the step boundary by `k_group_sumsq<true`.
+template <bool SGD, int MG>
+__global__ __launch_bounds__(256) void k_group_sumsq(const gm_tensor* __restrict__ tab, int nt,
+                                                     long long total, int ngroups, float gscale,
+                                                     float lr, long long chunk, double* __restrict__ rows) {
+    chunk_sums<SGD ? upd::sgd : upd::none, MG>(tab, nullptr, nt, total, ngroups, {gscale, lr, 0.f, 0.f}, chunk, rows);
+}
+
+template <bool SGD>
+__global__ __launch_bounds__(256) void k_group_sumsq_runs(const gm_tensor* __restrict__ tab, int nt,
+                                                          long long total, int ngroups, float gscale,
+                                                          float lr, long long chunk, double* __restrict__ rows) {
+    chunk_sums_runs<SGD ? upd::sgd : upd::none>(tab, nullptr, nt, total, ngroups, {gscale, lr, 0.f, 0.f}, chunk, rows);
+}
+
+template <bool MOM, int MG>
+__global__ __launch_bounds__(256) void k_group_sumsq_sgdm(const gm_tensor* __restrict__ tab,
+                                                          float* const* __restrict__ mom, int nt, long long total,
+                                                          int ngroups, sgdm_args h, long long chunk,
+                                                          double* __restrict__ rows) {
+    chunk_sums<MOM ? upd::mom : upd::decay, MG>(tab, mom, nt, total, ngroups, h, chunk, rows);
+}
+
 template <bool MOM>
 __global__ __launch_bounds__(256) void k_group_sumsq_sgdm_runs(const gm_tensor* __restrict__ tab,
                                                                float* const* __restrict__ mom, int nt,
                                                                long long total, int ngroups, sgdm_args h,
                                                                long long chunk, double* __restrict__ rows) {
-    __shared__ double sred[4][2];
-    __shared__ double acc[2 * kMaxGroups];
-    if (threadIdx.x < 2 * kMaxGroups) acc[threadIdx.x] = 0.0;
-    const long long e0 = (long long)blockIdx.x * chunk;
-    const long long e1 = min(total, e0 + chunk);
-    int ti = find_tensor(tab, nt, e0);
-    unsigned cur = tab[ti].group_mask;
-    double aw = 0.0, ag = 0.0;
-    long long e = e0;
-    while (e < e1) {
-        const gm_tensor T = tab[ti];
-        if (T.group_mask != cur) {
-            flush_run(aw, ag, cur, ngroups, sred, acc);
-            cur = T.group_mask;
-        }
-        const long long tb = e - T.offset;
-        const long long te = min(T.n, e1 - T.offset);
-        float sw = 0.f, sg = 0.f;
-        stream_segment_sgdm<MOM>(T, MOM ? mom[ti] : nullptr, tb, te, h, sw, sg);
-        aw += (double)sw;
-        ag += (double)sg;
-        e = T.offset + te;
-        ++ti;
-    }
-    flush_run(aw, ag, cur, ngroups, sred, acc);
-    if (threadIdx.x < 2 * ngroups) rows[(size_t)blockIdx.x * 2 * ngroups + threadIdx.x] = acc[threadIdx.x];
+    chunk_sums_runs<MOM ? upd::mom : upd::decay>(tab, mom, nt, total, ngroups, h, chunk, rows);
 }
 
 // 1024 threads stream the [nrows][w] row block as one flat array with fully coalesced
@@ -425,9 +345,15 @@ extern "C" size_t gm_group_sumsq_scratch(long long total) {
     return (size_t)nb * 2 * kMaxGroups * sizeof(double);
 }
 
-// the argument checks every entry point shares
-static int group_sumsq_args(const gm_tensor* table, int nt, long long total, int ngroups, const double* out,
-                            const void* scratch, size_t scratch_bytes) {
+// The launch path of every entry point: shared checks, chunking, the kernel of (form, group
+// count), finalize.  mom: the buffers of upd::mom; gate: optional (null: sums only).
+static int group_sumsq(const gm_tensor* table, float* const* mom, int nt, long long total, int ngroups,
+                       const sgdm_args& h, upd form, double* out, void* scratch, size_t scratch_bytes, void* gate,
+                       int gate_n, void* stream) {
+    // (main, bypass) groups per branch: 4 for the two-branch gate, 2 nb for the N-branch one (nb in
+    // the state: the rule reads 4 nb sums)
+    GM_REQUIRE(!gate || (gate_n ? (ngroups >= 4 && ngroups % 2 == 0) : ngroups == 4),
+               "group_sumsq_gate: %d groups do not match the %s gate", ngroups, gate_n ? "N-branch" : "two-branch");
     GM_REQUIRE(table && nt >= 1 && total >= 1, "group_sumsq: empty tensor table");
     GM_REQUIRE(ngroups >= 1 && ngroups <= kMaxGroups, "group_sumsq: ngroups must be 1..%d", kMaxGroups);
     GM_REQUIRE(out, "group_sumsq: null output");
@@ -435,55 +361,40 @@ static int group_sumsq_args(const gm_tensor* table, int nt, long long total, int
     GM_REQUIRE((total + chunk - 1) / chunk < (1ll << 31), "group_sumsq: too many elements");
     GM_REQUIRE(scratch && scratch_bytes >= gm_group_sumsq_scratch(total),
                "group_sumsq: scratch %zu < %zu bytes", scratch_bytes, gm_group_sumsq_scratch(total));
-    return 0;
-}
-
-// (main, bypass) groups per branch: 4 for the two-branch gate, 2 nb for the N-branch one (nb in
-// the state: the rule reads 4 nb sums)
-static int gate_groups(int ngroups, int gate_n) {
-    GM_REQUIRE(gate_n ? (ngroups >= 4 && ngroups % 2 == 0) : ngroups == 4,
-               "group_sumsq_gate: %d groups do not match the %s gate", ngroups, gate_n ? "N-branch" : "two-branch");
-    return 0;
-}
-
-static int group_sumsq(const gm_tensor* table, int nt, long long total, int ngroups, float gscale, float lr,
-                       double* out, void* scratch, size_t scratch_bytes, void* gate, int gate_n, void* stream) {
-    int rc0 = group_sumsq_args(table, nt, total, ngroups, out, scratch, scratch_bytes);
-    if (rc0) return rc0;
-    const long long chunk = chunk_elems(total);
-    const long long nb = (total + chunk - 1) / chunk;
+    const int nb = (int)((total + chunk - 1) / chunk);
     hipStream_t st = as_stream(stream);
     double* rows = (double*)scratch;
-    if (ngroups <= 8) {
-        if (lr != 0.f)
-            k_group_sumsq<true, 8><<<(int)nb, 256, 0, st>>>(table, nt, total, ngroups, gscale, lr, chunk, rows);
-        else
-            k_group_sumsq<false, 8><<<(int)nb, 256, 0, st>>>(table, nt, total, ngroups, gscale, lr, chunk, rows);
-    } else {  // N-branch gates (C5: 12 branches -> 24 groups)
-        if (lr != 0.f)
-            k_group_sumsq_runs<true><<<(int)nb, 256, 0, st>>>(table, nt, total, ngroups, gscale, lr, chunk, rows);
-        else
-            k_group_sumsq_runs<false><<<(int)nb, 256, 0, st>>>(table, nt, total, ngroups, gscale, lr, chunk, rows);
+    const bool few = ngroups <= 8;  // else the N-branch gates (C5: 12 branches -> 24 groups)
+    const bool plain = form == upd::none || form == upd::sgd;
+    if (plain) {
+        const bool sgd = form == upd::sgd;
+        const auto k = few ? (sgd ? k_group_sumsq<true, 8> : k_group_sumsq<false, 8>)
+                           : (sgd ? k_group_sumsq_runs<true> : k_group_sumsq_runs<false>);
+        k<<<nb, 256, 0, st>>>(table, nt, total, ngroups, h.gscale, h.lr, chunk, rows);
+    } else {
+        const bool mo = form == upd::mom;
+        const auto k = few ? (mo ? k_group_sumsq_sgdm<true, 8> : k_group_sumsq_sgdm<false, 8>)
+                           : (mo ? k_group_sumsq_sgdm_runs<true> : k_group_sumsq_sgdm_runs<false>);
+        k<<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h, chunk, rows);
     }
-    int rc = check_launch("k_group_sumsq");
+    int rc = check_launch(plain ? "k_group_sumsq" : "k_group_sumsq_sgdm");
     if (rc) return rc;
-    k_group_finalize<<<1, kFinT, 0, st>>>(rows, (int)nb, ngroups, out, gate, gate_n);
+    k_group_finalize<<<1, kFinT, 0, st>>>(rows, nb, ngroups, out, gate, gate && gate_n ? 1 : 0);
     return check_launch("k_group_finalize");
 }
 
 extern "C" int gm_group_sumsq(const gm_tensor* table, int nt, long long total, int ngroups, float gscale,
                               float lr, double* out, void* scratch, size_t scratch_bytes, void* stream) {
-    return group_sumsq(table, nt, total, ngroups, gscale, lr, out, scratch, scratch_bytes, nullptr, 0, stream);
+    return group_sumsq(table, nullptr, nt, total, ngroups, {gscale, lr, 0.f, 0.f}, lr != 0.f ? upd::sgd : upd::none,
+                       out, scratch, scratch_bytes, nullptr, 0, stream);
 }
 
 extern "C" int gm_group_sumsq_gate(const gm_tensor* table, int nt, long long total, int ngroups, float gscale,
                                    float lr, double* out, void* scratch, size_t scratch_bytes, void* gate,
                                    int gate_n, void* stream) {
     GM_REQUIRE(gate, "group_sumsq_gate: null gate state");
-    int rc = gate_groups(ngroups, gate_n);
-    if (rc) return rc;
-    return group_sumsq(table, nt, total, ngroups, gscale, lr, out, scratch, scratch_bytes, gate, gate_n ? 1 : 0,
-                       stream);
+    return group_sumsq(table, nullptr, nt, total, ngroups, {gscale, lr, 0.f, 0.f}, lr != 0.f ? upd::sgd : upd::none,
+                       out, scratch, scratch_bytes, gate, gate_n, stream);
 }
 
 extern "C" int gm_group_sumsq_sgdm(const gm_tensor* table, float* const* mom, int nt, long long total,
@@ -495,28 +406,6 @@ extern "C" int gm_group_sumsq_sgdm(const gm_tensor* table, float* const* mom, in
                "group_sumsq_sgdm: weight_decay must be finite and >= 0");
     GM_REQUIRE((mom != nullptr) == (momentum != 0.f),
                "group_sumsq_sgdm: momentum buffers must be given if and only if momentum != 0");
-    int rc = gate ? gate_groups(ngroups, gate_n) : 0;
-    if (rc) return rc;
-    rc = group_sumsq_args(table, nt, total, ngroups, out, scratch, scratch_bytes);
-    if (rc) return rc;
-    const long long chunk = chunk_elems(total);
-    const int nb = (int)((total + chunk - 1) / chunk);
-    hipStream_t st = as_stream(stream);
-    double* rows = (double*)scratch;
-    const sgdm_args h = {gscale, lr, momentum, weight_decay};
-    if (ngroups <= 8) {
-        if (mom)
-            k_group_sumsq_sgdm<true, 8><<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h, chunk, rows);
-        else
-            k_group_sumsq_sgdm<false, 8><<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h, chunk, rows);
-    } else {
-        if (mom)
-            k_group_sumsq_sgdm_runs<true><<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h, chunk, rows);
-        else
-            k_group_sumsq_sgdm_runs<false><<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h, chunk, rows);
-    }
-    rc = check_launch("k_group_sumsq_sgdm");
-    if (rc) return rc;
-    k_group_finalize<<<1, kFinT, 0, st>>>(rows, nb, ngroups, out, gate, gate && gate_n ? 1 : 0);
-    return check_launch("k_group_finalize");
+    return group_sumsq(table, mom, nt, total, ngroups, {gscale, lr, momentum, weight_decay},
+                       mom ? upd::mom : upd::decay, out, scratch, scratch_bytes, gate, gate_n, stream);
 }

@@ -458,8 +458,7 @@ class BalancedStep:
         if self.momentum != 0.0 or self.weight_decay != 0.0:  # gm_group_sumsq_sgdm
             kw = dict(momentum=self.momentum, weight_decay=self.weight_decay, momentum_buffers=self._mom_bufs)
         if self.device_gate:
-            return self.norms.sums(grad_scale=1.0 / self.world, lr=self.lr, gate=self.gate_state,
-                                   gate_n=self.gate_n, **kw)
+            kw.update(gate=self.gate_state, gate_n=self.gate_n)
         return self.norms.sums(grad_scale=1.0 / self.world, lr=self.lr, **kw)
 
     def momentum_buffer(self, p):

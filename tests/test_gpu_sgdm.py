@@ -3,7 +3,8 @@
 Kernel level (GroupNorms.sums with momentum / weight_decay): parameters and momentum buffers
 against torch.optim.SGD in float64 over consecutive steps, the group sums and the on-device
 gate's state against the plain entry points on clones, the scalar path (buffers not congruent
-with their parameters), skipped entries (no gradient), the many-group form.
+with their parameters), skipped entries (no gradient), the many-group form; every element of the
+update exactly on dyadic operands (test_update_is_exact_on_dyadic_operands).
 Engine level (BalancedStep(momentum=, weight_decay=)): each step's update recomputed in
 float64 from the flat buffers, the accessor, graph == eager, one-rank data parallel == no
 group, and the defaults untouched.
@@ -192,6 +193,98 @@ def test_many_group_form(dev):
 def test_many_group_form_without_momentum(dev):
     shapes, names = _twelve()
     _steps(dev, shapes, names, 2, 0.1, 0.0, 5e-4, seed=7)
+
+
+# ---------------------------------------------------------------------------------------
+# every element of the update, exactly (the contract of tests/exactint.py): integer parameters
+# and gradients in [-64, 64], zero buffers and dyadic hyper-parameters make g' = 0.5 g,
+# d = wd w + g', b' = mu b + d and w' = w - 0.125 b' dyadic rationals that fp32 holds exactly
+# for three steps, so any fma order or contraction gives the float64 recurrence's value.
+# ---------------------------------------------------------------------------------------
+EXACT_SCALE, EXACT_LR, EXACT_STEPS = 0.5, 0.125, 3
+EXACT_SETS = {"eight": lambda: (SHAPES8, TWO, "net_view_1.d"),
+              "twelve": lambda: _twelve() + ("net_view_3.conv.weight",)}
+# (mu, wd, buffers one float off congruence, one entry without a gradient); (0, 0): the plain entry
+EXACT_FORMS = {"momentum": (0.5, 0.25, False, False), "decay": (0.0, 0.25, False, False),
+               "plain": (0.0, 0.0, False, False), "momentum-scalar-path": (0.5, 0.25, True, False),
+               "momentum-skipped-entry": (0.5, 0.25, False, True)}
+
+
+def _exact_reference(shapes, mu, wd, nograd, seed):
+    """Start values, per-step gradients and the float64 recurrence's parameters and buffers after
+    each step, with every intermediate checked to round-trip through float32."""
+    def holds(t):
+        assert torch.equal(t.float().double(), t), "the operands do not keep the recurrence exact in fp32"
+        return t
+    g = torch.Generator().manual_seed(seed)
+    w = {n: torch.randint(-64, 65, s, generator=g).double() for n, s in shapes.items()}
+    b = {n: torch.zeros(s, dtype=torch.float64) for n, s in shapes.items()}
+    start, grads, after = {n: t.clone() for n, t in w.items()}, [], []
+    for _ in range(EXACT_STEPS):
+        gr = {n: torch.randint(-64, 65, s, generator=g).double() for n, s in shapes.items() if n not in nograd}
+        for n, t in gr.items():
+            d = holds(wd * w[n] + holds(EXACT_SCALE * t))
+            b[n] = holds(mu * b[n] + d)
+            w[n] = holds(w[n] - EXACT_LR * b[n])
+        grads.append(gr)
+        after.append(({n: t.clone() for n, t in w.items()}, {n: t.clone() for n, t in b.items()}))
+    return start, grads, after
+
+
+@pytest.mark.parametrize("form", EXACT_FORMS)
+@pytest.mark.parametrize("which", EXACT_SETS)
+def test_update_is_exact_on_dyadic_operands(dev, which, form):
+    """Parameters and buffers torch.equal the float64 recurrence after each of three steps; at
+    step 1 (integer w, per-thread partial sums below 2^24) the returned sums equal the host's
+    float64 sums exactly, from step 2 on the plain entry's on clones as in _steps."""
+    from greedy_multimodal_learning_amd.callbacks import GroupNorms
+    shapes, names, skipped = EXACT_SETS[which]()
+    mu, wd, skew, skip = EXACT_FORMS[form]
+    nograd = (skipped,) if skip else ()
+    start, grads, after = _exact_reference(shapes, mu, wd, nograd, seed=11)  # (asserts before any launch)
+    params = [(n, torch.nn.Parameter(w.float().to(dev))) for n, w in start.items()]
+    bufs = None
+    if mu != 0:
+        bufs = []
+        for n, p in params:
+            big = torch.zeros(p.numel() + 1, device=dev)
+            b = big[1:].view(p.shape) if skew else big[:-1].view(p.shape)
+            assert (b.data_ptr() - p.data_ptr()) % 16 == (4 if skew else 0)
+            if n in nograd:
+                b.fill_(SENTINEL)
+            bufs.append(b)
+    gn = GroupNorms(params, *names)
+    for k in range(1, EXACT_STEPS + 1):
+        clones = []
+        for n, p in params:
+            p.grad = grads[k - 1][n].float().to(dev) if n in grads[k - 1] else None
+            c = torch.nn.Parameter(p.detach().clone())
+            c.grad = None if p.grad is None else p.grad.clone()
+            clones.append((n, c))
+        want = GroupNorms(clones, *names).sums(grad_scale=EXACT_SCALE, lr=0.0)
+        out = gn.sums(grad_scale=EXACT_SCALE, lr=EXACT_LR, momentum=mu, weight_decay=wd, momentum_buffers=bufs)
+        if k == 1:
+            host = torch.zeros(2 * gn.ngroups, dtype=torch.float64)
+            for (n, _), m in zip(params, gn.masks):
+                sw = float((start[n] ** 2).sum())
+                sg = float(((EXACT_SCALE * grads[0][n]) ** 2).sum()) if n in grads[0] else 0.0
+                for j in range(gn.ngroups):
+                    if (m >> j) & 1:
+                        host[2 * j] += sw
+                        host[2 * j + 1] += sg
+            assert torch.equal(out.cpu(), host), (out.cpu() - host).abs().max()
+        elif not skew:
+            assert torch.equal(out, want), (k, (out - want).abs().max())
+        else:
+            torch.testing.assert_close(out, want, rtol=2e-6, atol=0)
+        ref_w, ref_b = after[k - 1]
+        for i, (n, p) in enumerate(params):
+            got = p.detach().double().cpu()
+            assert torch.equal(got, ref_w[n]), (n, k, float((got - ref_w[n]).abs().max()))
+            if bufs is not None:
+                got = bufs[i].double().cpu()
+                want_b = torch.full_like(got, SENTINEL) if n in nograd else ref_b[n]
+                assert torch.equal(got, want_b), (n + " (buffer)", k, float((got - want_b).abs().max()))
 
 
 def test_binding_refuses_misplaced_buffers(dev):
