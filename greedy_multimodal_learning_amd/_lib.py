@@ -334,6 +334,8 @@ EXPORTS.update({
     "gm_set_spin_limit": (c_int, [ctypes.c_uint]),
     "gm_bn_set_concurrency": (c_int, [c_int]),
     "gm_bn_set_fused_mode": (c_int, [c_int]),
+    "gm_bn_fused_form": (c_int, [ctypes.c_longlong, c_int, c_int, c_int]),
+    "gm_bn_plan_rows": (ctypes.c_longlong, [ctypes.c_longlong, c_int, c_int, c_int]),
     "gm_set_residency": (c_int, [c_int, c_int, c_int]),
     "gm_get_residency": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
 })

@@ -2310,6 +2310,22 @@ extern "C" int gm_bn_set_fused_mode(int mode) {
     return GM_OK;
 }
 
+// What the planner picks for a bf16 training launch of G groups of [M, C] under the mode,
+// concurrency and residency in effect: fused_plan's own return value.  Read-only.
+extern "C" int gm_bn_fused_form(long long M, int C, int bwd, int G) {
+    if (M <= 0 || C < 8 || C > kMaxC || (C & (C - 1)) != 0 || G < 1 || G > kMaxBnG) return 0;
+    Plan fp;
+    return fused_plan(M, C, fp, bwd != 0, G);
+}
+
+// Rows per workgroup of that launch (the fused plan's, or make_plan's on the two-launch path):
+// a thread sums rows / (256 / min(C, 64) * 8) of them in fp32, then the row groups are summed.
+extern "C" long long gm_bn_plan_rows(long long M, int C, int bwd, int G) {
+    if (M <= 0 || C < 8 || C > kMaxC || (C & (C - 1)) != 0 || G < 1 || G > kMaxBnG) return 0;
+    Plan fp;
+    return fused_plan(M, C, fp, bwd != 0, G) ? fp.rpb : make_plan(M, C).rpb;
+}
+
 // Statistics half of the training forward only (one reduce launch): save_mean/invstd,
 // running statistics, num_batches_tracked and the affine coefficients in coef_out
 // (required); no y.  The apply is fused into the consumer (gm_bn_relu_maxpool2d_fwd_bf16).

@@ -83,6 +83,13 @@ int gm_get_residency(int* streams, int* sharers, int* reserved_cus);
 /* 0: always the two-launch path; 1: single launch with register-held strips only;
  * 2 (default): also the streaming single-launch variant. */
 int gm_bn_set_fused_mode(int mode);
+/* The form a bf16 training BatchNorm launch of G groups of [M, C] takes under the mode,
+ * concurrency and residency in effect (bwd != 0: the backward): 4, 8 or 16 = single launch with
+ * that many register-held rows per thread, -1 = the streaming single launch, 0 = two launches.
+ * gm_bn_plan_rows: the rows per workgroup of that launch.  Both are read-only queries (they
+ * need the device for the occupancy they plan with) and change no launch. */
+int gm_bn_fused_form(long long M, int C, int bwd, int G);
+long long gm_bn_plan_rows(long long M, int C, int bwd, int G);
 
 /* ---------------------------------------------------------------------------
  * Spatial reduction per (batch, channel): the MMTM squeeze and its backward.

@@ -57,6 +57,19 @@ def _tensors(G, M, C, seed, strided, dev):
     return out
 
 
+def _regime(G, M, C, dev):
+    """The regime inputs of tests/bnregimes.py (|mean|/std ~ 26, var ~ 1e-4 and 0, negative, zero,
+    tiny and large gamma; a gradient with a mean, correlated with x): one case per group."""
+    import bnregimes as R
+    cs = [R.build((1, C, 1, M), R.seed((1, C, 1, M), g), res=True) for g in range(G)]
+    return cs, [c.gamma.to(dev) for c in cs], [c.beta.to(dev) for c in cs]
+
+
+def _fill(ts, srcs):
+    for t, s in zip(ts, srcs):
+        t.copy_(s.to(BF))
+
+
 def _rows_of(a, b, rows):
     """[C / 64][rows][64][2] partial rows: sums of a and b ([M, C] fp32) over `rows` disjoint
     pixel chunks (empty chunks, rows > M, are zero rows)."""
@@ -80,8 +93,9 @@ def _fwd_stats(xs, rows):
     return st
 
 
-def _run_fwd(xs, ress, relu, rows, nb, calls=1, mask=True, strided=True):
-    """Both arms `calls` times; returns per arm the list of every output tensor."""
+def _run_fwd(xs, ress, relu, rows, nb, calls=1, mask=True, strided=True, par=None):
+    """Both arms `calls` times; returns per arm the list of every output tensor.  par: the
+    groups' (gammas, betas) in place of the drawn ones."""
     L, lib = _lib()
     dev = xs[0].device
     G, (M, C) = len(xs), xs[0].shape
@@ -90,6 +104,8 @@ def _run_fwd(xs, ress, relu, rows, nb, calls=1, mask=True, strided=True):
     gam = [(torch.rand(C, generator=g) + 0.5).to(dev) for _ in range(G)]
     bet = [(torch.rand(C, generator=g) - 0.5).to(dev) for _ in range(G)]
     rm0 = [(torch.rand(C, generator=g) * 0.2 - 0.1).to(dev) for _ in range(G)]
+    if par is not None:
+        gam, bet = par
     stats0 = _fwd_stats(xs, rows)
     outs = []
     for arm in ("two", "fold"):
@@ -128,16 +144,22 @@ def _check(outs):
             _same(b[k], a[k], k)
 
 
-def _fwd_case(M, C, rows, G, res, relu, nb, strided=True, calls=1, poison=False):
+def _fwd_case(M, C, rows, G, res, relu, nb, strided=True, calls=1, poison=False, regime=False):
     dev = torch.device("cuda:0")
     xs = _tensors(G, M, C, 1000 * rows + M + C, strided, dev)
     ress = _tensors(G, M, C, 7 + M, strided, dev) if res else None
+    par = None
+    if regime:
+        cs, *par = _regime(G, M, C, dev)
+        _fill(xs, [c.x for c in cs])
+        if res:
+            _fill(ress, [c.res for c in cs])
     if poison:
         xs[0][M // 2, 3] = float("nan")
         xs[G - 1][M - 1, C - 1] = float("inf")
         if ress is not None:
             ress[0][0, 9] = float("nan")
-    outs = _run_fwd(xs, ress, relu, rows, nb, calls, strided=strided)
+    outs = _run_fwd(xs, ress, relu, rows, nb, calls, strided=strided, par=par)
     _check(outs)
     return outs
 
@@ -181,6 +203,12 @@ def test_forward_nan_inf(res):
     assert bool(outs[1]["y"].float().isnan().any())
 
 
+def test_forward_regime_inputs():
+    """The regime inputs through both arms (residual + ReLU with the mask bytes, two groups)."""
+    outs = _fwd_case(3136, 128, 25, 2, True, True, 5, regime=True)
+    assert int(outs[1]["mask"].count_nonzero()) > 0
+
+
 def test_forward_running_state_two_calls():
     outs = _fwd_case(105, 128, 33, 2, True, True, 3, calls=2)
     assert [int(v) for v in outs[1]["num_batches_tracked"]] == [2, 2]
@@ -214,7 +242,7 @@ def test_forward_rule_entry_matches():
 
 # ---- backward from producer statistics ---------------------------------------------------
 
-def _bwd_case(M, C, rows, G, relu, nb, accumulate, strided=True):
+def _bwd_case(M, C, rows, G, relu, nb, accumulate, strided=True, regime=False):
     L, lib = _lib()
     dev = torch.device("cuda:0")
     stream = L.stream_of(dev)
@@ -222,11 +250,16 @@ def _bwd_case(M, C, rows, G, relu, nb, accumulate, strided=True):
     dys = _tensors(G, M, C, 17 + M + C, strided, dev)
     g = torch.Generator().manual_seed(C + rows + M)
     gam = [(torch.rand(C, generator=g) + 0.5).to(dev) for _ in range(G)]
+    bet = [torch.full((C,), 0.1, device=dev) for _ in range(G)]
+    if regime:
+        cs, gam, bet = _regime(G, M, C, dev)
+        _fill(xs, [c.x for c in cs])
+        _fill(dys, [c.dy for c in cs])
     mean = torch.stack([x.float().mean(0) for x in xs])
     var = torch.stack([x.float().var(0, unbiased=False) for x in xs])
     invstd = (var + 1e-5).rsqrt()
     # the forward's coefficients: the mask is x * sc + sh > 0
-    fcoef = torch.stack([torch.cat([gam[i] * invstd[i], 0.1 - mean[i] * gam[i] * invstd[i]]) for i in range(G)])
+    fcoef = torch.stack([torch.cat([gam[i] * invstd[i], bet[i] - mean[i] * gam[i] * invstd[i]]) for i in range(G)])
     fcoef = fcoef.contiguous()
     off = lib.gm_bn_bwd_stats_coef_offset(C, G, rows)
     stats0 = torch.zeros(off + G * 4 * C, device=dev, dtype=torch.float32)
@@ -278,9 +311,14 @@ def test_backward(case, relu, accumulate):
     _bwd_case(M, C, rows, G, relu, nb, accumulate, strided)
 
 
+@pytest.mark.parametrize("relu", [False, True], ids=["norelu", "relu_from_x"])
+def test_backward_regime_inputs(relu):
+    _bwd_case(3136, 128, 33, 2, relu, 25, 0, False, regime=True)
+
+
 # ---- the residual-affine form (a downsample block's output) -------------------------------
 
-def _res_affine_case(M, C, rows, rrows, G, relu, nb, strided=True, poison=False):
+def _res_affine_case(M, C, rows, rrows, G, relu, nb, strided=True, poison=False, regime=False):
     L, lib = _lib()
     dev = torch.device("cuda:0")
     stream = L.stream_of(dev)
@@ -293,6 +331,11 @@ def _res_affine_case(M, C, rows, rrows, G, relu, nb, strided=True, poison=False)
     g = torch.Generator().manual_seed(C + rows + rrows)
     par = [[(torch.rand(C, generator=g) + 0.5).to(dev) for _ in range(G)] for _ in range(2)]   # gammas
     par += [[(torch.rand(C, generator=g) - 0.5).to(dev) for _ in range(G)] for _ in range(2)]  # betas
+    if regime:  # the block output's BatchNorm on groups 0 .. G - 1, the residual's on the next G cases
+        cs, *pz = _regime(2 * G, M, C, dev)
+        _fill(xs, [c.x for c in cs[:G]])
+        _fill(rs, [c.x for c in cs[G:]])
+        par = [pz[0][:G], pz[0][G:], pz[1][:G], pz[1][G:]]
     stats0, rstats0 = _fwd_stats(xs, rows), _fwd_stats(rs, rrows)
     outs = []
     for arm in ("separate", "res_affine"):
@@ -345,6 +388,13 @@ def _res_affine_case(M, C, rows, rrows, G, relu, nb, strided=True, poison=False)
 def test_forward_residual_affine_form():
     """The fifth residual / ReLU form, at the shape of test_forward_residual_relu_forms."""
     outs = _res_affine_case(3136, 128, 25, 49, 2, True, 5)
+    assert int(outs[1]["mask"].count_nonzero()) > 0
+
+
+def test_residual_affine_regime_inputs():
+    """Both BatchNorms of the residual-affine form on regime inputs: two affines with negative,
+    zero and large scales ahead of one ReLU."""
+    outs = _res_affine_case(3136, 128, 25, 49, 2, True, 5, regime=True)
     assert int(outs[1]["mask"].count_nonzero()) > 0
 
 

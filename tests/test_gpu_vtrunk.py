@@ -123,11 +123,14 @@ def test_grouped_stem_and_pool(dev):
 
 
 @pytest.mark.parametrize("mode", ["res_relu", "relu", "plain"])
-@pytest.mark.parametrize("shape", [(8, 64, 56, 56), (8, 256, 14, 14), (8, 512, 7, 7)],
+@pytest.mark.parametrize("shape", [(8, 64, 56, 56), (8, 256, 14, 14), (8, 512, 7, 7), (8, 128, 28, 28, "regimes")],
                          ids=lambda s: "x".join(map(str, s)))
 def test_grouped_bn_matches_per_view(dev, mode, shape):
+    """The last row draws its inputs and parameters from tests/bnregimes.py (|mean|/std ~ 26,
+    var ~ 1e-4 and 0, negative, zero, tiny and large gamma, a gradient with a mean)."""
     from greedy_multimodal_learning_amd.bn import GMBatchNorm2d
     from greedy_multimodal_learning_amd.vtrunk import vbn
+    regimes, shape = len(shape) == 5, shape[:4]
     N, C, H, W = shape
     G = 2
     g = torch.Generator().manual_seed(C + len(mode))
@@ -141,6 +144,15 @@ def test_grouped_bn_matches_per_view(dev, mode, shape):
             b.weight.uniform_(0.5, 1.5, generator=None)
             b.bias.uniform_(-0.5, 0.5)
             b.running_mean.uniform_(-0.1, 0.1)
+        if regimes:
+            import bnregimes as R
+            c = R.build(shape, R.seed(shape, i), res=True)
+            sl = slice(i * N, (i + 1) * N)
+            for t, src in ((x, c.x), (res, c.res), (gy, c.dy)):
+                t[sl] = R.nchw(src, shape).to(dev, torch.bfloat16)
+            with torch.no_grad():
+                b.weight.copy_(c.gamma)
+                b.bias.copy_(c.beta)
         r = GMBatchNorm2d(C).to(dev)
         r.load_state_dict(b.state_dict())
         bns.append(b.train())
