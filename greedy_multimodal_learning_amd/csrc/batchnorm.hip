@@ -14,9 +14,16 @@
 //      dgamma = S2*invstd, dx = a*dz + b*x + c per channel.
 //   2. k_bn_apply_bwd: dx (and dres = dz for the residual branch).
 // Bytes per element (bf16): fwd 2 (stats) + 4..6 (apply); bwd 4..6 + 6..8.
-// The reduce + apply kernels are templated on the element type E: bf16 (the
-// performance trunk) or fp32 (the reference-precision trunk, gm_bn_*_f32); the
-// single-launch fused kernels are bf16 only.
+// The apply kernels are templated on the element type E: bf16 (the performance trunk) or
+// fp32 (the reference-precision trunk, gm_bn_*_f32, whose reduce is k_bn_reduce_f64);
+// k_bn_reduce and the single-launch fused kernels are bf16 only.
+// Each shared part has one definition, in this order: the element rules (form_dz, form_dx,
+// form_y, store_y) and accum_vals; the per-channel coefficients (fwd_coef, bwd_coef), their
+// side outputs (fwd_store, bwd_store) and the batch counter (count_batch); the strip of a reduce
+// block (Strip, store_partial_row) and the partial-row combine (combine_rows); the folded
+// kernels' band_loop; the coefficient hand-off (combine_coefs, handoff_coefs); then the
+// kernels, and on the host launch_apply / launch_apply_bwd, apply_args, fwd_groups /
+// bwd_groups and the two shape rules (shape_ok, stats_shape_ok).
 #include <cstdlib>
 #include <initializer_list>
 #include <type_traits>
@@ -53,12 +60,7 @@ inline int ilog2(int v) {
     return l;
 }
 
-inline int bn_blocks() {
-    static int b = [] {
-        return 512;
-    }();
-    return b;
-}
+constexpr int kBnBlocks = 512;  // workgroups of a reduce launch (make_plan)
 
 inline Plan make_plan(long long M, int C) {
     Plan p;
@@ -66,7 +68,7 @@ inline Plan make_plan(long long M, int C) {
     p.tpr_log = ilog2(p.SW / 8);
     p.rpp = kT >> p.tpr_log;
     p.nslice = C / p.SW;
-    long long want = bn_blocks() / p.nslice;
+    long long want = kBnBlocks / p.nslice;
     if (M * C >= (16ll << 20)) want *= 2;  // large maps: bandwidth-bound, more blocks
     if (want < 1) want = 1;
     if (want > kMaxRC) want = kMaxRC;
@@ -116,13 +118,24 @@ __device__ __forceinline__ uint4 mask_vals(unsigned b) {
 // Pin loaded values at this point: every load issued before is complete here, and none is sunk
 // past it to its first use (the compiler otherwise issues a streaming loop's loads one round
 // trip at a time - the ReLU mask bytes after the 16-B vectors had landed)
-typedef unsigned pin_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // a 16-B vector as one register tuple
+__device__ __forceinline__ uint4 u4(u32x4 w) { return make_uint4(w.x, w.y, w.z, w.w); }
+__device__ __forceinline__ void pin(u32x4& v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void pin(u32x4& v, u32x4& w) { asm volatile("" : "+v"(v), "+v"(w)); }  // one wait for both
 __device__ __forceinline__ void pin(uint4& v) {
-    pin_u32x4 w = {v.x, v.y, v.z, v.w};
-    asm volatile("" : "+v"(w));
-    v = make_uint4(w.x, w.y, w.z, w.w);
+    u32x4 w = {v.x, v.y, v.z, v.w};
+    pin(w);
+    v = u4(w);
 }
 __device__ __forceinline__ void pin(unsigned& v) { asm volatile("" : "+v"(v)); }
+
+__device__ __forceinline__ uint4 ld_nt16(const uint4* p) {  // streamed once: nontemporal
+    return u4(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
+}
+__device__ __forceinline__ void st_nt16(uint4* p, uint4 v) {
+    const u32x4 w = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(p));
+}
 
 // Per-view-group operands: a grouped launch (gm_bn_*_grouped_bf16) normalises G views
 // stacked along the batch, each with its own parameters, statistics and scratch, in one
@@ -236,42 +249,51 @@ __device__ __forceinline__ bool wait_generation(const unsigned* gen, unsigned g0
 // (z = x*sc + sh > 0, the forward's own fp32 value) instead of read back from y
 enum { FWD = 0, BWD = 1, BWD_RELU = 2, BWD_RELUX = 3 };  // relu as a template arg: no per-load branch
 
-template <int MODE, typename E>
-__device__ __forceinline__ void accum(const ReduceArgs& a, long long v, const float* mu, float* s1, float* s2,
-                                      const float* fsc, const float* fsh) {
-    float xf[8];
-    V8<E>::ld(a.x, v, xf);
-    if (MODE == FWD) {
+// The element rules, each on 8 values (float[8]); every kernel below forms its values here.
+// dz: dy where the forward's ReLU passed - y > 0 on the stored output (BWD_RELU; yf may be the
+// mask_vals of its mask byte) or x*sc + sh > 0 recomputed (BWD_RELUX); BWD: dz = dy
+template <int MODE>
+__device__ __forceinline__ void form_dz(float* d, const float* xf, const float* yf, const float* fsc,
+                                        const float* fsh) {
+    if (MODE == BWD_RELU) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            s1[j] += xf[j];
-            s2[j] = fmaf(xf[j], xf[j], s2[j]);
-        }
-    } else {
-        float d[8];
-        V8<E>::ld(a.dy, v, d);
-        if (MODE == BWD_RELU) {
-            float yf[8];
-            V8<E>::ld(a.y, v, yf);
+        for (int j = 0; j < 8; ++j) d[j] = yf[j] > 0.f ? d[j] : 0.f;
+    }
+    if (MODE == BWD_RELUX) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = yf[j] > 0.f ? d[j] : 0.f;
-        }
-        if (MODE == BWD_RELUX) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = fmaf(xf[j], fsc[j], fsh[j]) > 0.f ? d[j] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            s1[j] += d[j];
-            s2[j] = fmaf(d[j], xf[j] - mu[j], s2[j]);
-        }
+        for (int j = 0; j < 8; ++j) d[j] = fmaf(xf[j], fsc[j], fsh[j]) > 0.f ? d[j] : 0.f;
     }
 }
+// dx = ca*dz + cb*x + cc, or (CENTER, the fp32 path) ca*dz + cb*(x - mean) + cc
+template <bool CENTER = false>
+__device__ __forceinline__ void form_dx(float* o, const float* d, const float* xf, const float* ca, const float* cb,
+                                        const float* cc, const float* mu = nullptr) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        o[j] = CENTER ? fmaf(ca[j], d[j], fmaf(cb[j], xf[j] - mu[j], cc[j])) : fmaf(ca[j], d[j], fmaf(cb[j], xf[j], cc[j]));
+}
+// y = relu?(x*sc + sh (+ r)) in place
+template <bool RES, bool RELU>
+__device__ __forceinline__ void form_y(float* f, const float* r, const float* sc, const float* sh) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float z = fmaf(f[j], sc[j], sh[j]);
+        if (RES) z += r[j];
+        f[j] = RELU ? relu_nan(z) : z;
+    }
+}
+// the bf16 store of y, with (MASK, where the caller gave a mask buffer) its ReLU mask byte
+template <bool MASK, typename I>
+__device__ __forceinline__ void store_y(uint4* y, uint8_t* mask, I i, const float* f) {
+    const uint4 w = pack8(f);
+    y[i] = w;
+    if (MASK && mask) mask[i] = (uint8_t)mask_byte(w);
+}
 
-// accum() on already loaded vectors (zero vectors contribute nothing in every mode)
+// one vector's terms of the statistics sums (zero vectors contribute nothing in every mode)
 template <int MODE>
 __device__ __forceinline__ void accum_vals(uint4 ux, uint4 ud, uint4 uy, const float* mu, float* s1, float* s2,
-                                          const float* fsc = nullptr, const float* fsh = nullptr) {
+                                           const float* fsc = nullptr, const float* fsh = nullptr) {
     float xf[8];
     unpack8(ux, xf);
     if (MODE == FWD) {
@@ -281,24 +303,27 @@ __device__ __forceinline__ void accum_vals(uint4 ux, uint4 ud, uint4 uy, const f
             s2[j] = fmaf(xf[j], xf[j], s2[j]);
         }
     } else {
-        float d[8];
+        float d[8], yf[8];
         unpack8(ud, d);
-        if (MODE == BWD_RELU) {
-            float yf[8];
-            unpack8(uy, yf);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = yf[j] > 0.f ? d[j] : 0.f;
-        }
-        if (MODE == BWD_RELUX) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = fmaf(xf[j], fsc[j], fsh[j]) > 0.f ? d[j] : 0.f;
-        }
+        if (MODE == BWD_RELU) unpack8(uy, yf);
+        form_dz<MODE>(d, xf, yf, fsc, fsh);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             s1[j] += d[j];
             s2[j] = fmaf(d[j], xf[j] - mu[j], s2[j]);
         }
     }
+}
+
+// accum_vals() on vector v of the launch's bf16 tensors
+template <int MODE>
+__device__ __forceinline__ void accum(const ReduceArgs& a, long long v, const float* mu, float* s1, float* s2,
+                                      const float* fsc, const float* fsh) {
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    const uint4 ux = static_cast<const uint4*>(a.x)[v];
+    const uint4 ud = MODE != FWD ? static_cast<const uint4*>(a.dy)[v] : z;
+    const uint4 uy = MODE == BWD_RELU ? static_cast<const uint4*>(a.y)[v] : z;
+    accum_vals<MODE>(ux, ud, uy, mu, s1, s2, fsc, fsh);
 }
 
 // per-channel operands of finalize(), loaded by every block BEFORE its ticket so the
@@ -375,6 +400,14 @@ __device__ __forceinline__ BwdCoef bwd_coef(double S1, double S2, double invM, c
     return k;
 }
 
+// num_batches_tracked += 1, by the thread that finalizes channel 0.  Not part of fwd_store: the
+// callers place its read-modify-write round trip where it overlaps their loads - in fwd_store it
+// sat between the coefficient stores and the generation word of the fused forward's hand-off,
+// 0.5 - 1.3 us per launch that every waiting block paid
+__device__ __forceinline__ void count_batch(const ReduceArgs& a, int c) {
+    if (a.nbt && c == 0) *a.nbt += 1;
+}
+
 // the side outputs of a finalize: statistics, running averages, coefficient area(s) (FWD);
 // coefficient area and parameter gradients (BWD)
 template <bool SC1>
@@ -448,95 +481,56 @@ __device__ __forceinline__ bool ticket(unsigned* ctr, unsigned n, float* flag) {
     return *flag != 0.f;
 }
 
-template <int MODE, bool SC1 = false>
-__device__ __forceinline__ void combine_finalize(const ReduceArgs& a, int cs, float* red, const FinOps& fo);
-
-// One launch: partial sums per (row chunk, channel slice) + one ticketed combine
-// per slice + per-channel finalize.
-template <int MODE, typename E>
-__global__ __launch_bounds__(kT) void k_bn_reduce(ReduceArgs a0) {
-    const ReduceArgs a = group_args(a0);
-    __shared__ float red[kRedF + 4];  // the one LDS object: row-group partials, flag
-    const int t = threadIdx.x;
-    const int C = a.C, SW = a.SW;
-    const int rc = blockIdx.x, cs = blockIdx.y;
-    const int tpr = 1 << a.tpr_log;
-    const int cg = t & (tpr - 1);
-    const int r0 = t >> a.tpr_log;
-    const int rpp = kT >> a.tpr_log;
-    const long long vpr = C >> 3;                     // 16-B vectors per row
-    const int c0 = cs * SW + cg * 8;                  // first channel of this thread
-
-    float fsc[8], fsh[8];
-    if (MODE == BWD_RELUX) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            fsc[j] = a.fcoef[c0 + j];
-            fsh[j] = a.fcoef[C + c0 + j];
-        }
+// A block's strip of the 2-D reduce grid (blockIdx.x = row chunk rc, blockIdx.y = slice cs):
+// thread t holds the 8 channels from c0 (vector cv of a row of vpr vectors) of the rows
+// r0, r0 + rpp, ... of [rbeg, rend).
+struct Strip {
+    int t, rc, cs, cg, r0, rpp, c0;
+    long long vpr, cv, rbeg, rend;
+    __device__ __forceinline__ explicit Strip(const ReduceArgs& a) {
+        t = threadIdx.x;
+        rc = blockIdx.x;
+        cs = blockIdx.y;
+        const int tpr = 1 << a.tpr_log;
+        cg = t & (tpr - 1);
+        r0 = t >> a.tpr_log;
+        rpp = kT >> a.tpr_log;
+        vpr = a.C >> 3;
+        c0 = cs * a.SW + cg * 8;
+        cv = c0 >> 3;
+        rbeg = (long long)rc * a.rpb;
+        rend = rbeg + a.rpb;
+        if (rend > a.M) rend = a.M;
     }
-    float mu[8];
-    if (MODE != FWD) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) mu[j] = a.save_mean[c0 + j];
-    }
-    float s1[8], s2[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s1[j] = s2[j] = 0.f;
+};
 
-    const long long rbeg = (long long)rc * a.rpb;
-    long long rend = rbeg + a.rpb;
-    if (rend > a.M) rend = a.M;
-    long long r = rbeg + r0;
-    const long long cv = c0 >> 3;
-    const long long st = (long long)rpp * vpr;
-    for (; r + 7 * rpp < rend; r += 8 * rpp) {
-        const long long v = r * vpr + cv;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) accum<MODE, E>(a, v + u * st, mu, s1, s2, fsc, fsh);
-    }
-    if (MODE == FWD && std::is_same<E, uint16_t>::value && r < rend) {  // the tail as ONE predicated batch
-        const uint4* X = static_cast<const uint4*>(a.x);
-        uint4 vx[8];
-        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) vx[u] = X[(r + u * rpp < rend ? r + u * rpp : r) * vpr + cv];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) accum_vals<MODE>(r + u * rpp < rend ? vx[u] : z, z, z, mu, s1, s2);
-    } else {
-        for (; r < rend; r += rpp) accum<MODE, E>(a, r * vpr + cv, mu, s1, s2, fsc, fsh);
-    }
-
-    // row-group combine in LDS: red[r0][SW][2]  (rpp * 2SW == 4096 floats)
-    const int S2w = 2 * SW;
+// row-group combine in LDS, red[r0][SW][2] (rpp * 2SW == 4096 values), then the block's partial
+// row with write-through stores (T: fp32 sums, or the fp64 sums of the reference-precision reduce)
+template <typename T>
+__device__ __forceinline__ void store_partial_row(const ReduceArgs& a, const Strip& sp, T* red, const T* s1,
+                                                  const T* s2) {
+    const int S2w = 2 * a.SW;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        red[r0 * S2w + (cg * 8 + j) * 2] = s1[j];
-        red[r0 * S2w + (cg * 8 + j) * 2 + 1] = s2[j];
+        red[sp.r0 * S2w + (sp.cg * 8 + j) * 2] = s1[j];
+        red[sp.r0 * S2w + (sp.cg * 8 + j) * 2 + 1] = s2[j];
     }
     __syncthreads();
-    float* p1 = a.part + ((size_t)cs * a.nrc + rc) * S2w;
-    if (t < S2w) {
-        float acc = 0.f;
-        for (int i = 0; i < rpp; ++i) acc += red[i * S2w + t];
-        st_sc1(&p1[t], acc);
+    T* p1 = reinterpret_cast<T*>(a.part) + ((size_t)sp.cs * a.nrc + sp.rc) * S2w;
+    if (sp.t < S2w) {
+        T acc = 0;
+        for (int i = 0; i < sp.rpp; ++i) acc += red[i * S2w + sp.t];
+        st_sc1(&p1[sp.t], acc);
     }
-    FinOps fo{};
-    if (t < SW) fo = fin_load<MODE>(a, cs * SW + t);  // in flight with the partial store
-    // the last block of the slice combines its nrc partial rows: lane group of L
-    // threads per row (one float4 each), G = 256/L row groups, rows g, g+G, ...
-    if (!ticket(a.counter + cs, (unsigned)a.nrc, &red[kRedF])) return;
-    combine_finalize<MODE>(a, cs, red, fo);
 }
 
-// The last block of a slice: combine the slice's nrc partial rows (lane group of L
-// threads per row, one float4 each, G = 256/L row groups, rows g, g+G, ...) in fp64
-// and finalize the slice's channels.
-template <int MODE, bool SC1>
-__device__ __forceinline__ void combine_finalize(const ReduceArgs& a, int cs, float* red, const FinOps& fo) {
+// Combine slice cs's nrc partial rows in fp64 (lane group of L threads per row, one float4
+// each, G = 256/L row groups, rows g, g+G, ...; 16-B sc1 loads, fixed order: every block that
+// combines computes the same sums) and call fin(t, S1, S2) in thread t < SW, channel cs * SW + t.
+template <typename F>
+__device__ __forceinline__ void combine_rows(const ReduceArgs& a, int cs, float* red, F fin) {
     const int t = threadIdx.x;
     const int SW = a.SW, S2w = 2 * SW;
-    if (MODE == FWD && a.nbt && cs == 0 && t == 0) *a.nbt += 1;
     const int L = S2w >> 2, G = kT / L;  // L in {4..32}, G in {8..64}
     const int lv = t % L, g = t / L;
     const auto rq = rsrc_of(a.part + (size_t)cs * a.nrc * S2w);
@@ -566,8 +560,72 @@ __device__ __forceinline__ void combine_finalize(const ReduceArgs& a, int cs, fl
             S1 += rd[i * S2w + 2 * t];
             S2 += rd[i * S2w + 2 * t + 1];
         }
-        finalize<MODE, SC1>(a, cs * SW + t, S1, S2, 1.0 / (double)a.M, fo);
+        fin(t, S1, S2);
     }
+}
+
+// The last block of a slice: combine the slice's partial rows and finalize its channels.
+template <int MODE, bool SC1 = false>
+__device__ __forceinline__ void combine_finalize(const ReduceArgs& a, int cs, float* red, const FinOps& fo) {
+    if (MODE == FWD) count_batch(a, cs * a.SW + threadIdx.x);  // ahead of the row loads
+    combine_rows(a, cs, red, [&](int t, double S1, double S2) {
+        finalize<MODE, SC1>(a, cs * a.SW + t, S1, S2, 1.0 / (double)a.M, fo);
+    });
+}
+
+// One launch: partial sums per (row chunk, channel slice) + one ticketed combine
+// per slice + per-channel finalize.  bf16 only (E is kept in the kernel's name); the fp32
+// reduce is k_bn_reduce_f64.
+template <int MODE, typename E>
+__global__ __launch_bounds__(kT) void k_bn_reduce(ReduceArgs a0) {
+    static_assert(std::is_same<E, uint16_t>::value, "k_bn_reduce: bf16 (fp32: k_bn_reduce_f64)");
+    const ReduceArgs a = group_args(a0);
+    __shared__ float red[kRedF + 4];  // the one LDS object: row-group partials, flag
+    const Strip sp(a);
+    const int C = a.C, SW = a.SW, c0 = sp.c0, rpp = sp.rpp;
+    const long long vpr = sp.vpr, cv = sp.cv, rend = sp.rend;
+
+    float fsc[8], fsh[8];
+    if (MODE == BWD_RELUX) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            fsc[j] = a.fcoef[c0 + j];
+            fsh[j] = a.fcoef[C + c0 + j];
+        }
+    }
+    float mu[8];
+    if (MODE != FWD) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) mu[j] = a.save_mean[c0 + j];
+    }
+    float s1[8], s2[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s1[j] = s2[j] = 0.f;
+
+    long long r = sp.rbeg + sp.r0;
+    const long long st = (long long)rpp * vpr;
+    for (; r + 7 * rpp < rend; r += 8 * rpp) {
+        const long long v = r * vpr + cv;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) accum<MODE>(a, v + u * st, mu, s1, s2, fsc, fsh);
+    }
+    if (MODE == FWD && r < rend) {  // the tail as ONE predicated batch
+        const uint4* X = static_cast<const uint4*>(a.x);
+        uint4 vx[8];
+        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) vx[u] = X[(r + u * rpp < rend ? r + u * rpp : r) * vpr + cv];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) accum_vals<MODE>(r + u * rpp < rend ? vx[u] : z, z, z, mu, s1, s2);
+    } else {
+        for (; r < rend; r += rpp) accum<MODE>(a, r * vpr + cv, mu, s1, s2, fsc, fsh);
+    }
+
+    store_partial_row(a, sp, red, s1, s2);
+    FinOps fo{};
+    if (sp.t < SW) fo = fin_load<MODE>(a, sp.cs * SW + sp.t);  // in flight with the partial store
+    if (!ticket(a.counter + sp.cs, (unsigned)a.nrc, &red[kRedF])) return;
+    combine_finalize<MODE>(a, sp.cs, red, fo);
 }
 
 // ---------------------------------------------------------------------------------
@@ -598,16 +656,6 @@ struct StemPoolGeo {
     const uint4* gp;         // [G*Ng][P][Q][C] bf16 pool gradient
     const uint4* xs;         // [G*Ng][P][Q][C] bf16 selected x (optional)
 };
-
-typedef unsigned u32x4v_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 ld_nt16(const uint4* p) {  // streamed once: nontemporal
-    const u32x4v_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4v_t*>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void st_nt16(uint4* p, uint4 v) {
-    const u32x4v_t w = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(w, reinterpret_cast<u32x4v_t*>(p));
-}
 
 template <bool APPLY>
 __global__ __launch_bounds__(kT) void k_stem_pool_bn_bwd(ReduceArgs a0, StemPoolGeo pg) {
@@ -713,6 +761,8 @@ __global__ __launch_bounds__(kT) void k_stem_pool_bn_bwd(ReduceArgs a0, StemPool
             }
             float xf[8];
             unpack8(it.xv[q], xf);
+            // (dz, dx and the partial row stay written out in this kernel: form_dz / form_dx /
+            // store_partial_row compute the same but moved its register figures, 120 -> 117, 229 -> 231)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float dr = __uint_as_float((uint32_t)Elem<uint16_t>::f2bf(d[j]) << 16);  // k_maxpool_bwd's bf16 dz
@@ -875,7 +925,7 @@ __global__ __launch_bounds__(kFinT) void k_bn_stats_finalize(ReduceArgs a0) {
     fin_combine(a, cs, rd, S1, S2);
     if (t < 64) {
         finalize<FWD>(a, cs * 64 + t, S1, S2, 1.0 / (double)a.M, fo);  // (rm / rv unused without rmean)
-        if (a.nbt && cs == 0 && t == 0) *a.nbt += 1;
+        count_batch(a, cs * 64 + t);
     }
 }
 
@@ -938,97 +988,85 @@ __device__ __forceinline__ ReduceArgs res_bn_args(const ReduceArgs& a, const Res
     return r;
 }
 
+// The predicated band loop of the folded kernels: the block's pixels p, p + st, ... of the slice's
+// 128-byte band, four pixels' 16-B loads in flight per thread - vector pixel * vpr + lane of A and
+// (TWO) of B, 32-bit offsets off a uniform base (the host checks M * C < 2^31) - and f(i, wa, wb)
+// per vector.  One loop, the ragged last batch predicated (pixels past M load pixel p's vectors
+// again and call nothing); M + 4 st < 2^32: no wrap.  SCHED: one vector's arithmetic at a time.
+template <bool TWO, bool SCHED, typename F>
+__device__ __forceinline__ void band_loop(const u32x4* A, const u32x4* B, unsigned M, unsigned vpr, F f) {
+    constexpr unsigned U = 4;
+    const int t = threadIdx.x;
+    const unsigned st = gridDim.x * (kFinT / 8);  // pixels per grid pass
+    unsigned p = blockIdx.x * (kFinT / 8) + (t >> 3);
+    const unsigned lane = t & 7;
+    for (; p < M; p += U * st) {
+        u32x4 ra[U], rb[U];
+#pragma unroll
+        for (unsigned u = 0; u < U; ++u) {
+            const unsigned q = p + u * st < M ? p + u * st : p;
+            ra[u] = A[q * vpr + lane];
+            if (TWO) rb[u] = B[q * vpr + lane];
+        }
+#pragma unroll
+        for (unsigned u = 0; u < U; ++u) {
+            if (TWO) pin(ra[u], rb[u]);
+            else pin(ra[u]);
+        }
+#pragma unroll
+        for (unsigned u = 0; u < U; ++u) {
+            if (p + u * st < M) f((p + u * st) * vpr + lane, ra[u], TWO ? rb[u] : ra[u]);
+            if (SCHED) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
 template <bool RES, bool RELU, bool RAFF>
 __device__ __forceinline__ void finalize_apply_body(const ReduceArgs& a0, const ResBn* rb) {
     const ReduceArgs a = group_args(a0);
     __shared__ double rd[kFinT / 32][128];
     __shared__ float cf[RAFF ? 4 : 2][64];
     const int t = threadIdx.x, cs = blockIdx.y;
-    const FinOps fo = fin_load_fwd_all(a, cs);
-    double S1, S2;
-    fin_combine(a, cs, rd, S1, S2);
-    if (t < 64) {
-        const FwdCoef k = fwd_coef(a, S1, S2, 1.0 / (double)a.M, fo);
-        cf[0][t] = k.sc;
-        cf[1][t] = k.sh;
-        if (blockIdx.x == 0) {
-            fwd_store<false>(a, cs * 64 + t, k);
-            if (a.nbt && cs == 0 && t == 0) *a.nbt += 1;
-        }
-    }
-    __syncthreads();
-    if (RAFF) {  // the residual's BatchNorm: the same combine and finalize on its own rows
-        const ReduceArgs ar = res_bn_args(a, *rb);
-        const FinOps fr = fin_load_fwd_all(ar, cs);
-        fin_combine(ar, cs, rd, S1, S2);  // (rd is free: every thread is past the barrier above)
+    // one BatchNorm's combine and finalize: sc / sh into cf[n], cf[n + 1]; block 0 stores the rest
+    auto fin_bn = [&](const ReduceArgs& b, int n) {
+        const FinOps fo = fin_load_fwd_all(b, cs);
+        double S1, S2;
+        fin_combine(b, cs, rd, S1, S2);
         if (t < 64) {
-            const FwdCoef k = fwd_coef(ar, S1, S2, 1.0 / (double)ar.M, fr);
-            cf[2][t] = k.sc;
-            cf[3][t] = k.sh;
+            const FwdCoef k = fwd_coef(b, S1, S2, 1.0 / (double)b.M, fo);
+            cf[n][t] = k.sc;
+            cf[n + 1][t] = k.sh;
             if (blockIdx.x == 0) {
-                fwd_store<false>(ar, cs * 64 + t, k);
-                if (ar.nbt && cs == 0 && t == 0) *ar.nbt += 1;
+                fwd_store<false>(b, cs * 64 + t, k);
+                count_batch(b, cs * 64 + t);
             }
         }
-        __syncthreads();
-    }
+        __syncthreads();  // (rd is free again: every thread is past this barrier)
+    };
+    fin_bn(a, 0);
+    if (RAFF) fin_bn(res_bn_args(a, *rb), 2);  // the residual's BatchNorm, on its own rows
     const int j8 = (t & 7) * 8;
     float sc[8], sh[8], rsc[8], rsh[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         sc[j] = cf[0][j8 + j];
         sh[j] = cf[1][j8 + j];
-        if (RAFF) {
+        if constexpr (RAFF) {
             rsc[j] = cf[2][j8 + j];
             rsh[j] = cf[3][j8 + j];
         }
     }
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    // 32-bit vector offsets off a uniform base (the host checks M * C < 2^31): this thread's
-    // vector of pixel p is p * vpr + (t & 7) of the slice's band
-    const unsigned vpr = (unsigned)a.C >> 3, M = (unsigned)a.M;
-    const u32x4* XX = static_cast<const u32x4*>(a.x) + cs * 8;
-    const u32x4* RR = reinterpret_cast<const u32x4*>(a.res) + cs * 8;
     uint4* YY = a.yout + cs * 8;
     uint8_t* MM = a.mask_out ? a.mask_out + cs * 8 : nullptr;
-    auto fin = [&](unsigned i, u32x4 wx, u32x4 wr) {
-        float f[8], r[8];
-        unpack8(make_uint4(wx.x, wx.y, wx.z, wx.w), f);
-        if (RES) unpack8(make_uint4(wr.x, wr.y, wr.z, wr.w), r);
-        if (RAFF) res_affine(r, rsc, rsh);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float z = fmaf(f[j], sc[j], sh[j]);
-            if (RES) z += r[j];
-            f[j] = RELU ? relu_nan(z) : z;
-        }
-        const uint4 o = pack8(f);
-        YY[i] = o;
-        if (RES && RELU && MM) MM[i] = (uint8_t)mask_byte(o);
-    };
-    constexpr unsigned U = 4;
-    const unsigned st = gridDim.x * (kFinT / 8);  // pixels per grid pass
-    unsigned p = blockIdx.x * (kFinT / 8) + (t >> 3);
-    const unsigned lane = t & 7;
-    // one loop, the ragged last batch predicated (pixels past M load pixel p's vector again and
-    // store nothing); M + 4 st < 2^32: no wrap
-    for (; p < M; p += U * st) {
-        u32x4 rx[U], rr[U];
-#pragma unroll
-        for (unsigned u = 0; u < U; ++u) {
-            const unsigned q = p + u * st < M ? p + u * st : p;
-            rx[u] = XX[q * vpr + lane];
-            if (RES) rr[u] = RR[q * vpr + lane];
-        }
-#pragma unroll
-        for (unsigned u = 0; u < U; ++u) {
-            asm volatile("" : "+v"(rx[u]));
-            if (RES) asm volatile("" : "+v"(rr[u]));
-        }
-#pragma unroll
-        for (unsigned u = 0; u < U; ++u)
-            if (p + u * st < M) fin((p + u * st) * vpr + lane, rx[u], RES ? rr[u] : rx[u]);
-    }
+    band_loop<RES, false>(static_cast<const u32x4*>(a.x) + cs * 8, reinterpret_cast<const u32x4*>(a.res) + cs * 8,
+                          (unsigned)a.M, (unsigned)a.C >> 3, [&](unsigned i, u32x4 wx, u32x4 wr) {
+                              float f[8], r[8];
+                              unpack8(u4(wx), f);
+                              if (RES) unpack8(u4(wr), r);
+                              if (RAFF) res_affine(r, rsc, rsh);
+                              form_y<RES, RELU>(f, r, sc, sh);
+                              store_y<RES && RELU>(YY, MM, i, f);
+                          });
 }
 
 template <bool RES, bool RELU>
@@ -1076,43 +1114,17 @@ __global__ __launch_bounds__(kFinT) void k_bn_bwd_finalize_apply(ReduceArgs a0, 
         cb[j] = cf[1][j8 + j];
         cc[j] = cf[2][j8 + j];
     }
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const unsigned vpr = (unsigned)a.C >> 3, M = (unsigned)a.M;  // 32-bit offsets as k_bn_finalize_apply
-    const u32x4* DY = static_cast<const u32x4*>(a.dy) + cs * 8;
-    const u32x4* XX = static_cast<const u32x4*>(a.x) + cs * 8;
     uint4* DX = a.yout + cs * 8;
-    auto out = [&](unsigned i, u32x4 wd, u32x4 wx) {
-        float d[8], xf[8], o[8];
-        unpack8(make_uint4(wd.x, wd.y, wd.z, wd.w), d);
-        unpack8(make_uint4(wx.x, wx.y, wx.z, wx.w), xf);
-        if (RELU) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = fmaf(xf[j], fs[j], fh[j]) > 0.f ? d[j] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = fmaf(ca[j], d[j], fmaf(cb[j], xf[j], cc[j]));
-        DX[i] = pack8(o);
-    };
-    constexpr unsigned U = 4;
-    const unsigned st = gridDim.x * (kFinT / 8);
-    unsigned p = blockIdx.x * (kFinT / 8) + (t >> 3);
-    const unsigned lane = t & 7;
-    for (; p < M; p += U * st) {  // the ragged last batch predicated, as k_bn_finalize_apply
-        u32x4 rdy[U], rx[U];
-#pragma unroll
-        for (unsigned u = 0; u < U; ++u) {
-            const unsigned q = p + u * st < M ? p + u * st : p;
-            rdy[u] = DY[q * vpr + lane];
-            rx[u] = XX[q * vpr + lane];
-        }
-#pragma unroll
-        for (unsigned u = 0; u < U; ++u) asm volatile("" : "+v"(rdy[u]), "+v"(rx[u]));
-#pragma unroll
-        for (unsigned u = 0; u < U; ++u) {
-            if (p + u * st < M) out((p + u * st) * vpr + lane, rdy[u], rx[u]);
-            __builtin_amdgcn_sched_barrier(0);  // one vector's arithmetic at a time: 128 VGPRs, no scratch
-        }
-    }
+    // (SCHED: one vector's arithmetic at a time keeps the kernel at 128 VGPRs, no scratch)
+    band_loop<true, true>(static_cast<const u32x4*>(a.dy) + cs * 8, static_cast<const u32x4*>(a.x) + cs * 8,
+                          (unsigned)a.M, (unsigned)a.C >> 3, [&](unsigned i, u32x4 wd, u32x4 wx) {
+                              float d[8], xf[8], o[8];
+                              unpack8(u4(wd), d);
+                              unpack8(u4(wx), xf);
+                              form_dz<RELU ? BWD_RELUX : BWD>(d, xf, nullptr, fs, fh);
+                              form_dx(o, d, xf, ca, cb, cc);
+                              DX[i] = pack8(o);
+                          });
 }
 
 // ---------------------------------------------------------------------------------
@@ -1125,7 +1137,7 @@ __global__ __launch_bounds__(kFinT) void k_bn_bwd_finalize_apply(ReduceArgs a0, 
 // partial rows (sc1 loads, fp64, the fixed order of combine_finalize: every block computes
 // the same coefficients) and keeps the coefficients in LDS; the block whose ticket came
 // last also writes the side outputs (statistics, running averages, counter, coef_out /
-// dgamma, dbeta) through finalize().  The counter then counts a second round (each block
+// dgamma, dbeta) through fwd_store / bwd_store.  The counter then counts a second round (each block
 // once it has seen nrc arrivals), and the block completing that round re-zeroes it, so
 // no poller can miss the value nrc and the ticket words are zero between calls again.
 __device__ __forceinline__ bool arrive(unsigned* ctr, unsigned n, float* flag) {
@@ -1164,65 +1176,94 @@ __device__ __forceinline__ void depart(unsigned* ctr, unsigned n) {
     }
 }
 
-// the slice's coefficients into cf[3][SW] (LDS): FWD sc, sh; BWD ca, cb, cc (bf16 form)
+// the slice's coefficients into cf[3][SW] (LDS): FWD sc, sh; BWD ca, cb, cc (bf16 form) - one
+// fwd_coef / bwd_coef per channel, which the last-arriving block also stores (side outputs)
 template <int MODE>
 __device__ __forceinline__ void combine_coefs(const ReduceArgs& a, int cs, float* red, const FinOps& fo, bool last,
                                               float* cf) {
-    const int t = threadIdx.x;
-    const int SW = a.SW, S2w = 2 * SW;
-    const int L = S2w >> 2, G = kT / L;
-    const int lv = t % L, g = t / L;
-    const auto rq = rsrc_of(a.part + (size_t)cs * a.nrc * S2w);
-    double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0;
-    for (int i0 = g; i0 < a.nrc; i0 += 8 * G) {
-        float4 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = i0 + u * G;
-            v[u] = i < a.nrc ? ld_sc1_f32x4(rq, (unsigned)(i * S2w + 4 * lv) * 4u) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            d0 += (double)v[u].x; d1 += (double)v[u].y; d2 += (double)v[u].z; d3 += (double)v[u].w;
-        }
-    }
-    __syncthreads();
-    double* rd = reinterpret_cast<double*>(red);
-    rd[g * S2w + 4 * lv + 0] = d0;
-    rd[g * S2w + 4 * lv + 1] = d1;
-    rd[g * S2w + 4 * lv + 2] = d2;
-    rd[g * S2w + 4 * lv + 3] = d3;
-    __syncthreads();
-    if (t < SW) {
-        double S1 = 0.0, S2 = 0.0;
-        for (int i = 0; i < G; ++i) {
-            S1 += rd[i * S2w + 2 * t];
-            S2 += rd[i * S2w + 2 * t + 1];
-        }
+    const int SW = a.SW;
+    combine_rows(a, cs, red, [&](int t, double S1, double S2) {
         const double invM = 1.0 / (double)a.M;
         const int c = cs * SW + t;
-        if (last) {
-            if (MODE == FWD && a.nbt && cs == 0 && t == 0) *a.nbt += 1;
-            finalize<MODE, false>(a, c, S1, S2, invM, fo);
-        }
-        const double gg = (double)fo.g;
         if (MODE == FWD) {
-            const double mean = S1 * invM;
-            double var = S2 * invM - mean * mean;
-            if (var < 0.0) var = 0.0;
-            const double invstd = 1.0 / sqrt(var + (double)a.eps);
-            const double sc = gg * invstd;
-            cf[t] = (float)sc;
-            cf[SW + t] = (float)((double)fo.b - mean * sc);
+            if (last) count_batch(a, c);  // (its load in flight over the coefficient arithmetic)
+            const FwdCoef k = fwd_coef(a, S1, S2, invM, fo);
+            if (last) fwd_store<false>(a, c, k);
+            cf[t] = k.sc;
+            cf[SW + t] = k.sh;
         } else {
-            const double mean = (double)fo.rm, is = (double)fo.rv;
-            const double ca = gg * is, cb = -gg * is * is * is * S2 * invM;
-            cf[t] = (float)ca;
-            cf[SW + t] = (float)cb;
-            cf[2 * SW + t] = (float)(-ca * S1 * invM - cb * mean);
+            const BwdCoef k = bwd_coef<false>(S1, S2, invM, fo);
+            if (last) bwd_store<false, false>(a, c, k);
+            cf[t] = k.ca;
+            cf[SW + t] = k.cb;
+            cf[2 * SW + t] = k.cc;
+        }
+    });
+    __syncthreads();
+}
+
+// the slice's generation word before the block's own work (thread 0; the others hold 0)
+__device__ __forceinline__ unsigned gen_read(const ReduceArgs& a, int cs) {
+    return threadIdx.x == 0 ? __hip_atomic_load(a.gen + cs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+}
+
+// The coefficient hand-off of the single-launch kernels, after the block's partial row is stored:
+// the redundant form above (a.redundant), or the slice's last block (ticket) finalizes and
+// publishes the coefficients (write-through stores, then the generation word g0 + 1) while the
+// others poll that word (bounded) and read them back with sc1 loads.  Fills this thread's N
+// coefficient vectors co[N][8] (FWD: sc, sh; BWD: ca, cb, cc) - NaN where the wait timed out:
+// never stale coefficients (the fault word is set) - and returns whether they are fresh.
+template <int MODE>
+__device__ __forceinline__ bool handoff_coefs(const ReduceArgs& a, const Strip& sp, float* red, unsigned g0,
+                                              float (*co)[8]) {
+    constexpr int N = MODE == FWD ? 2 : 3;
+    const int C = a.C, SW = a.SW, cs = sp.cs;
+    FinOps fo{};
+    if (sp.t < SW) fo = fin_load<MODE>(a, cs * SW + sp.t);
+    bool fresh = true;
+    if (a.redundant) {
+        __shared__ float cf[3 * 64];
+        const bool last = arrive(a.counter + cs, (unsigned)a.nrc, &red[kRedF]);
+        fresh = wait_count(a.counter + cs, (unsigned)a.nrc, a.spin_limit, &red[kRedF + 1]);
+        combine_coefs<MODE>(a, cs, red, fo, last, cf);
+        depart(a.counter + cs, (unsigned)a.nrc);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+#pragma unroll
+            for (int n = 0; n < N; ++n) co[n][j] = cf[n * SW + sp.cg * 8 + j];
+        }
+    } else {
+        unsigned* gen = a.gen + cs;
+        if (ticket(a.counter + cs, (unsigned)a.nrc, &red[kRedF])) {
+            combine_finalize<MODE, true>(a, cs, red, fo);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (sp.t == 0) __hip_atomic_store(gen, g0 + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            fresh = wait_generation(gen, g0, a.spin_limit, &red[kRedF + 1]);
+        }
+        const auto rq = rsrc_of(a.coef);
+        float4 lo[N], hi[N];
+#pragma unroll
+        for (int n = 0; n < N; ++n) {
+            lo[n] = ld_sc1_f32x4(rq, (unsigned)(n * C + sp.c0) * 4u);
+            hi[n] = ld_sc1_f32x4(rq, (unsigned)(n * C + sp.c0 + 4) * 4u);
+        }
+#pragma unroll
+        for (int n = 0; n < N; ++n) {
+            float* o = co[n];
+            o[0] = lo[n].x; o[1] = lo[n].y; o[2] = lo[n].z; o[3] = lo[n].w;
+            o[4] = hi[n].x; o[5] = hi[n].y; o[6] = hi[n].z; o[7] = hi[n].w;
         }
     }
-    __syncthreads();
+    if (!fresh) {
+#pragma unroll
+        for (int n = 0; n < N; ++n) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) co[n][j] = __builtin_nanf("");
+        }
+    }
+    return fresh;
 }
 
 // The reference-precision (fp32) reduce: the reference's CPU BatchNorm accumulates its
@@ -1236,43 +1277,29 @@ __global__ __launch_bounds__(kT) void k_bn_reduce_f64(ReduceArgs a0) {
     const ReduceArgs a = group_args(a0);
     __shared__ double red[kRedF];  // rpp * 2 * SW == 4096 doubles
     __shared__ float flag;
-    const int t = threadIdx.x;
-    const int C = a.C, SW = a.SW;
-    const int rc = blockIdx.x, cs = blockIdx.y;
-    const int tpr = 1 << a.tpr_log;
-    const int cg = t & (tpr - 1);
-    const int r0 = t >> a.tpr_log;
-    const int rpp = kT >> a.tpr_log;
-    const long long vpr = C >> 3;
-    const int c0 = cs * SW + cg * 8;
+    const Strip sp(a);
+    const int t = sp.t, C = a.C, SW = a.SW, cs = sp.cs, c0 = sp.c0;
     const float* X = static_cast<const float*>(a.x);
     const float* DY = static_cast<const float*>(a.dy);
     const float* Y = static_cast<const float*>(a.y);
-    double fsc[8], fsh[8], mu[8], s1[8], s2[8];
+    float fsc[8], fsh[8];
+    double mu[8], s1[8], s2[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        fsc[j] = MODE == BWD_RELUX ? (double)a.fcoef[c0 + j] : 0.0;
-        fsh[j] = MODE == BWD_RELUX ? (double)a.fcoef[C + c0 + j] : 0.0;
+        fsc[j] = MODE == BWD_RELUX ? a.fcoef[c0 + j] : 0.f;
+        fsh[j] = MODE == BWD_RELUX ? a.fcoef[C + c0 + j] : 0.f;
         mu[j] = MODE != FWD ? (double)a.save_mean[c0 + j] : 0.0;
         s1[j] = s2[j] = 0.0;
     }
-    const long long rbeg = (long long)rc * a.rpb;
-    long long rend = rbeg + a.rpb;
-    if (rend > a.M) rend = a.M;
-    for (long long r = rbeg + r0; r < rend; r += rpp) {
+    for (long long r = sp.rbeg + sp.r0; r < sp.rend; r += sp.rpp) {
         const long long e = r * C + c0;
-        float xf[8], d[8];
+        float xf[8], d[8], yf[8];
         V8<float>::ld(X + e, 0, xf);
         if (MODE != FWD) V8<float>::ld(DY + e, 0, d);
-        if (MODE == BWD_RELU) {
-            float yf[8];
-            V8<float>::ld(Y + e, 0, yf);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = yf[j] > 0.f ? d[j] : 0.f;
-        }
+        if (MODE == BWD_RELU) V8<float>::ld(Y + e, 0, yf);
+        if (MODE != FWD) form_dz<MODE>(d, xf, yf, fsc, fsh);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            if (MODE == BWD_RELUX) d[j] = fmaf(xf[j], (float)fsc[j], (float)fsh[j]) > 0.f ? d[j] : 0.f;
             if (MODE == FWD) {
                 s1[j] += (double)xf[j];
                 s2[j] = fma((double)xf[j], (double)xf[j], s2[j]);
@@ -1282,23 +1309,12 @@ __global__ __launch_bounds__(kT) void k_bn_reduce_f64(ReduceArgs a0) {
             }
         }
     }
+    store_partial_row(a, sp, red, s1, s2);
     const int S2w = 2 * SW;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        red[r0 * S2w + (cg * 8 + j) * 2] = s1[j];
-        red[r0 * S2w + (cg * 8 + j) * 2 + 1] = s2[j];
-    }
-    __syncthreads();
-    double* p1 = reinterpret_cast<double*>(a.part) + ((size_t)cs * a.nrc + rc) * S2w;
-    if (t < S2w) {
-        double acc = 0.0;
-        for (int i = 0; i < rpp; ++i) acc += red[i * S2w + t];
-        st_sc1(&p1[t], acc);
-    }
     FinOps fo{};
     if (t < SW) fo = fin_load<MODE>(a, cs * SW + t);
     if (!ticket(a.counter + cs, (unsigned)a.nrc, &flag)) return;
-    if (MODE == FWD && a.nbt && cs == 0 && t == 0) *a.nbt += 1;
+    if (MODE == FWD) count_batch(a, cs * SW + t);
     const double* pp = reinterpret_cast<const double*>(a.part) + (size_t)cs * a.nrc * S2w;
     if (t < S2w) {  // fixed order over the row chunks
         double acc = 0.0;
@@ -1321,24 +1337,12 @@ template <bool RES, bool RELU, int NR>
 __global__ __launch_bounds__(kT, NR == 16 ? 2 : NR == 8 ? 3 : 4) void k_bn_fwd_fused(ReduceArgs a0) {  // NR 0: streaming
     const ReduceArgs a = group_args(a0);
     __shared__ float red[kRedF + 4];
-    const int t = threadIdx.x;
-    const int C = a.C, SW = a.SW;
-    const int rc = blockIdx.x, cs = blockIdx.y;
-    const int tpr = 1 << a.tpr_log;
-    const int cg = t & (tpr - 1);
-    const int r0 = t >> a.tpr_log;
-    const int rpp = kT >> a.tpr_log;
-    const long long vpr = C >> 3;
-    const int c0 = cs * SW + cg * 8;
-    const long long cv = c0 >> 3;
-    unsigned* gen = a.gen + cs;
-    unsigned g0 = 0;
-    if (t == 0) g0 = __hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const Strip sp(a);
+    const int r0 = sp.r0, rpp = sp.rpp;
+    const long long vpr = sp.vpr, cv = sp.cv, rbeg = sp.rbeg, rend = sp.rend;
+    const unsigned g0 = gen_read(a, sp.cs);
     const uint4* X = static_cast<const uint4*>(a.x);
 
-    const long long rbeg = (long long)rc * a.rpb;
-    long long rend = rbeg + a.rpb;
-    if (rend > a.M) rend = a.M;
     const uint4 z = make_uint4(0u, 0u, 0u, 0u);
     constexpr int NV = NR > 0 ? NR : 1;
     uint4 v[NV];
@@ -1355,6 +1359,8 @@ __global__ __launch_bounds__(kT, NR == 16 ? 2 : NR == 8 ? 3 : 4) void k_bn_fwd_f
 #pragma unroll
         for (int u = 0; u < NV; ++u) accum_vals<FWD>(v[u], z, z, nullptr, s1, s2);
     } else {  // streaming: 8 rows in flight per thread, x re-read (L2 / MALL) by the apply
+        // (this loop and the apply's stay written out, as k_bn_bwd_fused's: behind one walker
+        // taking the per-vector action the streaming forms ran 1.5 % slower)
         long long r = rbeg + r0;
         const long long st = (long long)rpp * vpr;
         for (; r + 7 * rpp < rend; r += 8 * rpp) {
@@ -1367,67 +1373,23 @@ __global__ __launch_bounds__(kT, NR == 16 ? 2 : NR == 8 ? 3 : 4) void k_bn_fwd_f
         for (; r < rend; r += rpp) accum_vals<FWD>(X[r * vpr + cv], z, z, nullptr, s1, s2);
     }
 
-    const int S2w = 2 * SW;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        red[r0 * S2w + (cg * 8 + j) * 2] = s1[j];
-        red[r0 * S2w + (cg * 8 + j) * 2 + 1] = s2[j];
-    }
-    __syncthreads();
-    float* p1 = a.part + ((size_t)cs * a.nrc + rc) * S2w;
-    if (t < S2w) {
-        float acc = 0.f;
-        for (int i = 0; i < rpp; ++i) acc += red[i * S2w + t];
-        st_sc1(&p1[t], acc);
-    }
-    FinOps fo{};
-    if (t < SW) fo = fin_load<FWD>(a, cs * SW + t);
-    bool fresh = true;
-    float sc[8], sh[8];
-    if (a.redundant) {
-        __shared__ float cf[3 * 64];
-        const bool last = arrive(a.counter + cs, (unsigned)a.nrc, &red[kRedF]);
-        fresh = wait_count(a.counter + cs, (unsigned)a.nrc, a.spin_limit, &red[kRedF + 1]);
-        combine_coefs<FWD>(a, cs, red, fo, last, cf);
-        depart(a.counter + cs, (unsigned)a.nrc);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            sc[j] = cf[cg * 8 + j];
-            sh[j] = cf[SW + cg * 8 + j];
-        }
-    } else {
-        if (ticket(a.counter + cs, (unsigned)a.nrc, &red[kRedF])) {
-            combine_finalize<FWD, true>(a, cs, red, fo);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (t == 0) __hip_atomic_store(gen, g0 + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            fresh = wait_generation(gen, g0, a.spin_limit, &red[kRedF + 1]);
-        }
-        const auto rq = rsrc_of(a.coef);
-        const float4 sa = ld_sc1_f32x4(rq, (unsigned)c0 * 4u), sb = ld_sc1_f32x4(rq, (unsigned)(c0 + 4) * 4u);
-        const float4 ha = ld_sc1_f32x4(rq, (unsigned)(C + c0) * 4u), hb = ld_sc1_f32x4(rq, (unsigned)(C + c0 + 4) * 4u);
-        sc[0] = sa.x; sc[1] = sa.y; sc[2] = sa.z; sc[3] = sa.w; sc[4] = sb.x; sc[5] = sb.y; sc[6] = sb.z; sc[7] = sb.w;
-        sh[0] = ha.x; sh[1] = ha.y; sh[2] = ha.z; sh[3] = ha.w; sh[4] = hb.x; sh[5] = hb.y; sh[6] = hb.z; sh[7] = hb.w;
-    }
-    if (!fresh) {  // timed out: never apply stale coefficients (the fault word is set)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sc[j] = sh[j] = __builtin_nanf("");
-    }
+    store_partial_row(a, sp, red, s1, s2);
+    float co[2][8];
+    const bool fresh = handoff_coefs<FWD>(a, sp, red, g0, co);
     auto apply = [&](uint4 xv, long long i) {
         float f[8], q[8];
         unpack8(xv, f);
         if (RES) unpack8(a.res[i], q);
+        // (form_y's loop written out: the poison select belongs inside it - after it, the compiler
+        // drops the coefficients' own poison and waits for them inside every output block)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            float zz = fmaf(f[j], sc[j], sh[j]);
+            float zz = fmaf(f[j], co[0][j], co[1][j]);
             if (RES) zz += q[j];
             f[j] = RELU ? relu_nan(zz) : zz;
             if (!fresh) f[j] = __builtin_nanf("");  // poisoned (fmaxf would turn NaN into 0)
         }
-        const uint4 w = pack8(f);
-        a.yout[i] = w;
-        if (RES && RELU && a.mask_out) a.mask_out[i] = (uint8_t)mask_byte(w);
+        store_y<RES && RELU>(a.yout, a.mask_out, i, f);
     };
     if (NR > 0) {
 #pragma unroll
@@ -1449,6 +1411,12 @@ __global__ __launch_bounds__(kT, NR == 16 ? 2 : NR == 8 ? 3 : 4) void k_bn_fwd_f
     }
 }
 
+// y for the ReLU mask, or (YM) the forward's mask byte expanded to 1.0 / 0 bf16 values
+template <bool YM>
+__device__ __forceinline__ uint4 ld_ymask(const ReduceArgs& a, long long i) {
+    return YM ? mask_vals(a.ymask[i]) : static_cast<const uint4*>(a.y)[i];
+}
+
 // Fused backward, same scheme as k_bn_fwd_fused: the block holds its x / dy (/ y)
 // strip in registers (NR 4 or 8) or re-reads it (NR 0), the slice's last block
 // publishes (a, b, c) and every block writes dx = a*dz + b*x + c (and dres = dz).
@@ -1456,24 +1424,15 @@ template <int MODE, bool DRES, int NR, bool YM = false>
 __global__ __launch_bounds__(kT, NR == 8 ? 2 : 3) void k_bn_bwd_fused(ReduceArgs a0) {
     const ReduceArgs a = group_args(a0);
     __shared__ float red[kRedF + 4];
-    const int t = threadIdx.x;
-    const int C = a.C, SW = a.SW;
-    const int rc = blockIdx.x, cs = blockIdx.y;
-    const int tpr = 1 << a.tpr_log;
-    const int cg = t & (tpr - 1);
-    const int r0 = t >> a.tpr_log;
-    const int rpp = kT >> a.tpr_log;
-    const long long vpr = C >> 3;
-    const int c0 = cs * SW + cg * 8;
-    const long long cv = c0 >> 3;
-    unsigned* gen = a.gen + cs;
-    unsigned g0 = 0;
-    if (t == 0) g0 = __hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const Strip sp(a);
+    const int C = a.C, r0 = sp.r0, rpp = sp.rpp, c0 = sp.c0;
+    const long long vpr = sp.vpr, cv = sp.cv, rbeg = sp.rbeg, rend = sp.rend;
+    const unsigned g0 = gen_read(a, sp.cs);
     const uint4* X = static_cast<const uint4*>(a.x);
     const uint4* DY = static_cast<const uint4*>(a.dy);
     const uint4* Y = static_cast<const uint4*>(a.y);
-    // y for the ReLU mask, or (YM) the forward's mask byte expanded to 1.0 / 0 bf16 values
-    auto ldy = [&](long long i) { return YM ? mask_vals(a.ymask[i]) : Y[i]; };
+    // streaming rows in flight (register budget: y's vectors; the mask bytes (YM) cost one each)
+    constexpr int US = MODE == BWD_RELU && !YM ? 2 : 4;
     float mu[8], fsc[8], fsh[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -1483,14 +1442,9 @@ __global__ __launch_bounds__(kT, NR == 8 ? 2 : 3) void k_bn_bwd_fused(ReduceArgs
             fsh[j] = a.fcoef[C + c0 + j];
         }
     }
-    const long long rbeg = (long long)rc * a.rpb;
-    long long rend = rbeg + a.rpb;
-    if (rend > a.M) rend = a.M;
     const uint4 z = make_uint4(0u, 0u, 0u, 0u);
     constexpr int NV = NR > 0 ? NR : 1;
     constexpr int NY = MODE == BWD_RELU ? NV : 1;
-    // streaming rows in flight (register budget: y's vectors; the mask bytes (YM) cost one each)
-    constexpr int US = MODE == BWD_RELU && !YM ? 2 : 4;
     uint4 vx[NV], vd[NV], vy[NY];
     float s1[8], s2[8];
 #pragma unroll
@@ -1503,12 +1457,15 @@ __global__ __launch_bounds__(kT, NR == 8 ? 2 : 3) void k_bn_bwd_fused(ReduceArgs
             const uint4 wx = X[i], wd = DY[i];
             vx[u] = r < rend ? wx : z;
             vd[u] = r < rend ? wd : z;
-            if (MODE == BWD_RELU) vy[u] = ldy(i);
+            if (MODE == BWD_RELU) vy[u] = ld_ymask<YM>(a, i);
         }
 #pragma unroll
         for (int u = 0; u < NV; ++u)
             accum_vals<MODE>(vx[u], vd[u], MODE == BWD_RELU ? vy[u < NY ? u : 0] : z, mu, s1, s2, fsc, fsh);
     } else {
+        // streaming: US rows' loads in flight, every load of a batch issued before the first use
+        // (pin).  This loop and its twin in the output pass stay written out: behind one walker
+        // taking the per-vector action, three forms' register allocation lost a wave per SIMD.
         long long r = rbeg + r0;
         const long long st = (long long)rpp * vpr;
         for (; r + (US - 1) * rpp < rend; r += US * rpp) {
@@ -1531,85 +1488,25 @@ __global__ __launch_bounds__(kT, NR == 8 ? 2 : 3) void k_bn_bwd_fused(ReduceArgs
             }
 #pragma unroll
             for (int u = 0; u < US; ++u)
-                accum_vals<MODE>(wx[u], wd[u], MODE == BWD_RELU ? (YM ? mask_vals(wm[u]) : wy[u]) : z, mu, s1, s2, fsc,
-                                 fsh);
+                accum_vals<MODE>(wx[u], wd[u], MODE == BWD_RELU ? (YM ? mask_vals(wm[u]) : wy[u]) : z, mu, s1, s2, fsc, fsh);
         }
         for (; r < rend; r += rpp) {
             const long long i = r * vpr + cv;
-            accum_vals<MODE>(X[i], DY[i], MODE == BWD_RELU ? ldy(i) : z, mu, s1, s2, fsc, fsh);
+            accum_vals<MODE>(X[i], DY[i], MODE == BWD_RELU ? ld_ymask<YM>(a, i) : z, mu, s1, s2, fsc, fsh);
         }
     }
 
-    const int S2w = 2 * SW;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        red[r0 * S2w + (cg * 8 + j) * 2] = s1[j];
-        red[r0 * S2w + (cg * 8 + j) * 2 + 1] = s2[j];
-    }
-    __syncthreads();
-    float* p1 = a.part + ((size_t)cs * a.nrc + rc) * S2w;
-    if (t < S2w) {
-        float acc = 0.f;
-        for (int i = 0; i < rpp; ++i) acc += red[i * S2w + t];
-        st_sc1(&p1[t], acc);
-    }
-    FinOps fo{};
-    if (t < SW) fo = fin_load<MODE>(a, cs * SW + t);
-    bool fresh = true;
-    float ca[8], cb[8], cc[8];
-    if (a.redundant) {
-        __shared__ float cf[3 * 64];
-        const bool last = arrive(a.counter + cs, (unsigned)a.nrc, &red[kRedF]);
-        fresh = wait_count(a.counter + cs, (unsigned)a.nrc, a.spin_limit, &red[kRedF + 1]);
-        combine_coefs<MODE>(a, cs, red, fo, last, cf);
-        depart(a.counter + cs, (unsigned)a.nrc);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            ca[j] = cf[cg * 8 + j];
-            cb[j] = cf[SW + cg * 8 + j];
-            cc[j] = cf[2 * SW + cg * 8 + j];
-        }
-    } else {
-        if (ticket(a.counter + cs, (unsigned)a.nrc, &red[kRedF])) {
-            combine_finalize<MODE, true>(a, cs, red, fo);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (t == 0) __hip_atomic_store(gen, g0 + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            fresh = wait_generation(gen, g0, a.spin_limit, &red[kRedF + 1]);
-        }
-        const auto rq = rsrc_of(a.coef);
-        auto ld8 = [&](int off, float* o) {
-            const float4 p = ld_sc1_f32x4(rq, (unsigned)(off + c0) * 4u), q = ld_sc1_f32x4(rq, (unsigned)(off + c0 + 4) * 4u);
-            o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = p.w; o[4] = q.x; o[5] = q.y; o[6] = q.z; o[7] = q.w;
-        };
-        ld8(0, ca);
-        ld8(C, cb);
-        ld8(2 * C, cc);
-    }
-    if (!fresh) {  // timed out: never apply stale coefficients (the fault word is set)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ca[j] = cb[j] = cc[j] = __builtin_nanf("");
-    }
+    store_partial_row(a, sp, red, s1, s2);
+    float co[3][8];
+    handoff_coefs<MODE>(a, sp, red, g0, co);
     auto out = [&](uint4 ux, uint4 ud, uint4 uy, long long i) {
-        float d[8], xf[8];
+        float d[8], xf[8], yf[8], o[8];
         unpack8(ud, d);
         unpack8(ux, xf);
-        if (MODE == BWD_RELU) {
-            float yf[8];
-            unpack8(uy, yf);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = yf[j] > 0.f ? d[j] : 0.f;
-        }
-        if (MODE == BWD_RELUX) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = fmaf(xf[j], fsc[j], fsh[j]) > 0.f ? d[j] : 0.f;
-        }
+        if (MODE == BWD_RELU) unpack8(uy, yf);
+        form_dz<MODE>(d, xf, yf, fsc, fsh);
         if (DRES) a.dres_out[i] = pack8(d);
-        float o[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            o[j] = fmaf(ca[j], d[j], fmaf(cb[j], xf[j], cc[j]));
+        form_dx(o, d, xf, co[0], co[1], co[2]);
         a.yout[i] = pack8(o);
     };
     if (NR > 0) {
@@ -1645,7 +1542,7 @@ __global__ __launch_bounds__(kT, NR == 8 ? 2 : 3) void k_bn_bwd_fused(ReduceArgs
         }
         for (; r < rend; r += rpp) {
             const long long i = r * vpr + cv;
-            out(X[i], DY[i], MODE == BWD_RELU ? ldy(i) : z, i);
+            out(X[i], DY[i], MODE == BWD_RELU ? ld_ymask<YM>(a, i) : z, i);
         }
     }
 }
@@ -1693,14 +1590,9 @@ __global__ __launch_bounds__(kT) void k_bn_apply(ApplyArgs a) {
     }
     auto fin = [&](long long i, float* f, float* r) {
         if (RAFF) res_affine(r, rsc, rsh);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float z = fmaf(f[j], sc[j], sh[j]);
-            if (RES) z += r[j];
-            f[j] = RELU ? relu_nan(z) : z;
-        }
-        V8<E>::st(a.out, i, f);
-        if (RES && RELU && std::is_same<E, uint16_t>::value && a.mask_out) a.mask_out[i] = (uint8_t)mask_byte(pack8(f));
+        form_y<RES, RELU>(f, r, sc, sh);
+        if constexpr (std::is_same<E, uint16_t>::value) store_y<RES && RELU>(static_cast<uint4*>(a.out), a.mask_out, i, f);
+        else V8<E>::st(a.out, i, f);
     };
     auto one = [&](long long i) {
         i += go;
@@ -1712,7 +1604,6 @@ __global__ __launch_bounds__(kT) void k_bn_apply(ApplyArgs a) {
     };
     if constexpr (std::is_same<E, uint16_t>::value) {
         // four vectors' 16-B loads issued before the first use (as k_bn_apply_bwd)
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         constexpr int U = 4;
         const u32x4* XX = static_cast<const u32x4*>(a.x) + go;
         const u32x4* RR = static_cast<const u32x4*>(a.res) + go;
@@ -1725,14 +1616,14 @@ __global__ __launch_bounds__(kT) void k_bn_apply(ApplyArgs a) {
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                asm volatile("" : "+v"(rx[u]));
-                if (RES) asm volatile("" : "+v"(rr[u]));
+                pin(rx[u]);
+                if (RES) pin(rr[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 float f[8], r[8];
-                unpack8(make_uint4(rx[u].x, rx[u].y, rx[u].z, rx[u].w), f);
-                if (RES) unpack8(make_uint4(rr[u].x, rr[u].y, rr[u].z, rr[u].w), r);
+                unpack8(u4(rx[u]), f);
+                if (RES) unpack8(u4(rr[u]), r);
                 fin(go + v + u * stride, f, r);
             }
         }
@@ -1769,30 +1660,21 @@ __global__ __launch_bounds__(kT) void k_bn_apply_bwd(ApplyArgs a) {
         V8<E>::ld(a.x, go + i, xf);
         if (YR) V8<E>::ld(a.res, go + i, yf);
     };
+    constexpr int MODE = !RELU ? BWD : MASKX ? BWD_RELUX : BWD_RELU;
     auto out = [&](long long i, float* d, const float* xf, const float* yf) {
-        if (RELU && MASKX) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = fmaf(xf[j], fs[j], fh[j]) > 0.f ? d[j] : 0.f;
-        } else if (RELU) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = yf[j] > 0.f ? d[j] : 0.f;
-        }
+        form_dz<MODE>(d, xf, yf, fs, fh);
         if (DRES) V8<E>::st(a.out2, go + i, d);
         float o[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            o[j] = CENTER ? fmaf(ca[j], d[j], fmaf(cb[j], xf[j] - mu[j], cc[j])) : fmaf(ca[j], d[j], fmaf(cb[j], xf[j], cc[j]));
+        form_dx<CENTER>(o, d, xf, ca, cb, cc, mu);
         V8<E>::st(a.out, go + i, o);
     };
     // U vectors' loads issued before the first store (the pointers may alias as far as the
     // compiler knows: one vector at a time serialised load -> wait -> store, 32 B in flight)
     constexpr int U = 4;
     if constexpr (std::is_same<E, uint16_t>::value) {  // raw 16-B loads first, unpacked after
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         const u32x4* DY = static_cast<const u32x4*>(a.dy) + go;
         const u32x4* XX = static_cast<const u32x4*>(a.x) + go;
         const u32x4* YY = static_cast<const u32x4*>(a.res) + go;
-        auto u4 = [](u32x4 w) { return make_uint4(w.x, w.y, w.z, w.w); };
         for (; v + (U - 1) * stride < a.nvec; v += U * stride) {
             u32x4 rd[U], rx[U], ry[U];
 #pragma unroll
@@ -1805,8 +1687,8 @@ __global__ __launch_bounds__(kT) void k_bn_apply_bwd(ApplyArgs a) {
             // its use: one vector's 32 B in flight per thread)
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                asm volatile("" : "+v"(rd[u]), "+v"(rx[u]));
-                if (YR) asm volatile("" : "+v"(ry[u]));
+                pin(rd[u], rx[u]);
+                if (YR) pin(ry[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -1833,8 +1715,10 @@ __global__ __launch_bounds__(kT) void k_bn_apply_bwd(ApplyArgs a) {
     }
 }
 
-__global__ void k_bn_infer_coef(int C, const float* gamma, const float* beta, const float* rm, const float* rv,
-                                float eps, float* coef) {
+// the inference coefficients of channel c = blockIdx.x * blockDim.x + threadIdx.x (fp64 from the
+// running statistics, one rounding each): both kernels below, so the two agree bit for bit
+__device__ __forceinline__ void infer_coef(int C, const float* gamma, const float* beta, const float* rm,
+                                           const float* rv, float eps, float* coef) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const double is = 1.0 / sqrt((double)rv[c] + (double)eps);
@@ -1843,27 +1727,66 @@ __global__ void k_bn_infer_coef(int C, const float* gamma, const float* beta, co
     coef[C + c] = (float)((double)beta[c] - (double)rm[c] * sc);
 }
 
-// The same coefficients for a table of BatchNorms in one launch (gm_bn_infer_coef): entry
-// blockIdx.y, the arithmetic of k_bn_infer_coef term for term, so the two agree bit for bit.
-__global__ void k_bn_infer_coef_table(const gm_bn_coef_entry* tab) {
-    const gm_bn_coef_entry e = tab[blockIdx.y];
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    const int C = e.C;
-    if (c >= C) return;
-    const double is = 1.0 / sqrt((double)e.running_var[c] + (double)e.eps);
-    const double sc = (double)e.gamma[c] * is;
-    e.coef[c] = (float)sc;
-    e.coef[C + c] = (float)((double)e.beta[c] - (double)e.running_mean[c] * sc);
+__global__ void k_bn_infer_coef(int C, const float* gamma, const float* beta, const float* rm, const float* rv,
+                                float eps, float* coef) {
+    infer_coef(C, gamma, beta, rm, rv, eps, coef);
 }
 
-inline int apply_grid(long long nvec, int C) {
+// The same coefficients for a table of BatchNorms in one launch (gm_bn_infer_coef): entry blockIdx.y
+__global__ void k_bn_infer_coef_table(const gm_bn_coef_entry* tab) {
+    const gm_bn_coef_entry e = tab[blockIdx.y];
+    infer_coef(e.C, e.gamma, e.beta, e.running_mean, e.running_var, e.eps, e.coef);
+}
+
+inline int apply_grid(long long nvec) {
     // ~4 vectors per thread, grid a multiple of nothing in particular: kT is a
     // multiple of C/8 so the channel group of a thread is fixed
     long long g = (nvec + kT * 4 - 1) / (kT * 4);
     if (g > 8192) g = 8192;
     if (g < 1) g = 1;
-    (void)C;
     return (int)g;
+}
+
+// the fields every apply launch shares; the caller adds its tensors and coefficient areas
+inline ApplyArgs apply_args(long long M, int C, int relu) {
+    ApplyArgs b{};
+    b.nvec = M * (C / 8);
+    b.tpr_log = ilog2(C / 8);
+    b.C = C;
+    b.relu = relu;
+    return b;
+}
+
+// the template switches of the two apply kernels (raff: the residual-affine form, bf16 only)
+template <typename E>
+void launch_apply(bool res, bool relu, bool raff, dim3 g, hipStream_t st, const ApplyArgs& b) {
+    if constexpr (std::is_same<E, uint16_t>::value) {
+        if (raff) {
+            if (relu) hipLaunchKernelGGL((k_bn_apply<true, true, E, true>), g, dim3(kT), 0, st, b);
+            else hipLaunchKernelGGL((k_bn_apply<true, false, E, true>), g, dim3(kT), 0, st, b);
+            return;
+        }
+    }
+    if (res) {
+        if (relu) hipLaunchKernelGGL((k_bn_apply<true, true, E>), g, dim3(kT), 0, st, b);
+        else hipLaunchKernelGGL((k_bn_apply<true, false, E>), g, dim3(kT), 0, st, b);
+    } else {
+        if (relu) hipLaunchKernelGGL((k_bn_apply<false, true, E>), g, dim3(kT), 0, st, b);
+        else hipLaunchKernelGGL((k_bn_apply<false, false, E>), g, dim3(kT), 0, st, b);
+    }
+}
+
+template <typename E>
+void launch_apply_bwd(bool relu, bool dres, bool maskx, dim3 g, hipStream_t st, const ApplyArgs& b) {
+    if (maskx) {
+        hipLaunchKernelGGL((k_bn_apply_bwd<true, false, true, E>), g, dim3(kT), 0, st, b);
+    } else if (relu) {
+        if (dres) hipLaunchKernelGGL((k_bn_apply_bwd<true, true, false, E>), g, dim3(kT), 0, st, b);
+        else hipLaunchKernelGGL((k_bn_apply_bwd<true, false, false, E>), g, dim3(kT), 0, st, b);
+    } else {
+        if (dres) hipLaunchKernelGGL((k_bn_apply_bwd<false, true, false, E>), g, dim3(kT), 0, st, b);
+        else hipLaunchKernelGGL((k_bn_apply_bwd<false, false, false, E>), g, dim3(kT), 0, st, b);
+    }
 }
 
 constexpr int kGenOff = 32;  // generation words: header words [32, 32 + nslice) (nslice <= 32)
@@ -1879,13 +1802,8 @@ constexpr int kGenOff = 32;  // generation words: header words [32, 32 + nslice)
 // cannot be scheduled (the spin is bounded and then faults loudly, see wait_generation).
 // Returns NR (pl rewritten), -1 for the streaming variant (x re-read by the apply phase;
 // gm_bn_set_fused_mode(1) disables it) or 0: use the two-kernel path (gm_bn_set_fused_mode(0)).
-int g_concurrency = [] {
-    const int v = 4;
-    return v >= 1 ? v : 4;  // 0 / garbage: the default (never a division by zero)
-}();
-int g_fused_env = [] {
-    return 2;  // read once; 0 = two-kernel path, 1 = no streaming variant
-}();
+int g_concurrency = 4;  // gm_bn_set_concurrency (>= 1: never a division by zero)
+int g_fused_env = 2;    // gm_bn_set_fused_mode: 0 = two-kernel path, 1 = no streaming variant
 
 template <typename K>
 int occ_min(std::initializer_list<K> ks) {
@@ -1934,10 +1852,8 @@ int device_cus() {
 
 // the redundant-finalize hand-off (every block combines the partial rows): small maps only,
 // where a block's extra partial-row reads are a few KB
-static int g_bn_redundant_max = [] {
-    return 16;  // measured: 8 / 16 help layer 4 (~1-1.3 us a launch), 32+ slow layer 3
-}();
-inline int redundant_ok(int nrc) { return nrc <= g_bn_redundant_max ? 1 : 0; }
+constexpr int kRedundantMax = 16;  // measured: 8 / 16 help layer 4 (~1-1.3 us a launch), 32+ slow layer 3
+inline int redundant_ok(int nrc) { return nrc <= kRedundantMax ? 1 : 0; }
 
 inline int fused_plan(long long M, int C, Plan& pl, bool bwd = false, int G = 1) {
     if (g_fused_env == 0) return 0;
@@ -1952,41 +1868,36 @@ inline int fused_plan(long long M, int C, Plan& pl, bool bwd = false, int G = 1)
     const Occ& oc = occupancy();
     const int nrs[3] = {4, 8, 16};
     const int occ_reg[3] = {bwd ? oc.bwd[0] : oc.fwd[0], bwd ? oc.bwd[1] : oc.fwd[1], bwd ? 0 : oc.fwd[2]};
-    for (int i = 0; i < 3; ++i) {
-        if (occ_reg[i] <= 0) continue;
-        const long long budget = (long long)cus * occ_reg[i] / conc;
-        long long want = budget / base.nslice;
-        if (want < 1) continue;
+    // the co-resident grid of a kernel with occupancy occ: pl, if it fits the base plan's partials
+    // area and (max_nr > 0) a thread's rows fit max_nr registers-held vectors
+    auto fit = [&](int occ, int max_nr) {
+        const long long want = (long long)cus * occ / conc / base.nslice;
+        if (want < 1) return false;
         long long rpb = (M + want - 1) / want;
         rpb = (rpb + base.rpp - 1) / base.rpp * base.rpp;
-        if (rpb / base.rpp > nrs[i]) continue;
+        if (max_nr > 0 && rpb / base.rpp > max_nr) return false;
         const long long nrc = (M + rpb - 1) / rpb;
-        if (nrc > base.nrc) continue;  // partials area sized by the base plan
+        if (nrc > base.nrc) return false;  // partials area sized by the base plan
         pl = base;
         pl.rpb = rpb;
         pl.nrc = (int)nrc;
-        return nrs[i];
-    }
-    if (g_fused_env >= 2) {  // streaming variant: any map size
-        const int occ_s = bwd ? oc.bwd[2] : oc.fwd[3];
-        long long want = (long long)cus * occ_s / conc / base.nslice;
-        if (want >= 1) {
-            long long rpb = (M + want - 1) / want;
-            rpb = (rpb + base.rpp - 1) / base.rpp * base.rpp;
-            const long long nrc = (M + rpb - 1) / rpb;
-            if (nrc <= base.nrc) {
-                pl = base;
-                pl.rpb = rpb;
-                pl.nrc = (int)nrc;
-                return -1;
-            }
-        }
-    }
+        return true;
+    };
+    for (int i = 0; i < 3; ++i)
+        if (fit(occ_reg[i], nrs[i])) return nrs[i];
+    if (g_fused_env >= 2 && fit(bwd ? oc.bwd[2] : oc.fwd[3], 0)) return -1;  // streaming variant: any map size
     return 0;
 }
 
+// the two shape rules: a training / planning call's map, and a producer statistics buffer's
+// (whole 64-channel slices of partial rows)
+inline bool shape_ok(long long M, int C) { return M > 0 && C >= 8 && C <= kMaxC && (C & (C - 1)) == 0; }
+inline bool stats_shape_ok(const float* stats, int rows, int C) {
+    return stats && rows >= 1 && C >= 64 && C % 64 == 0;
+}
+
 int check_common(long long M, int C, const void* scratch, size_t bytes, const char* fn) {
-    if (M <= 0 || C < 8 || C > kMaxC || (C & (C - 1)) != 0) {
+    if (!shape_ok(M, C)) {
         set_error("%s: need M > 0 and C a power of two in [8, %d] (M=%lld C=%d)", fn, kMaxC, M, C);
         return GM_E_ARG;
     }
@@ -2079,13 +1990,8 @@ int check_scratch(long long M, int C, int G, bool grouped, const void* scratch, 
     return GM_OK;
 }
 
-// shared fields from group 0, per-group pointers into grp[], scratch split per group
-void fill_fwd(ReduceArgs& a, const gm_bn_fwd* ps, int G, bool grouped, const Plan& pl, char* s) {
-    const gm_bn_fwd* p = ps;
-    a.M = p->M; a.C = p->C; a.tpr_log = pl.tpr_log; a.rpb = pl.rpb;
-    a.SW = pl.SW; a.nrc = pl.nrc;
-    a.momentum = p->momentum; a.eps = p->eps;
-    set_scratch(a, pl, s, grouped);
+// the per-group pointers of a forward / backward call into grp[] (kernels read grp[] only)
+void fwd_groups(ReduceArgs& a, const gm_bn_fwd* ps, int G) {
     for (int g = 0; g < G; ++g) {
         BnGroup& q = a.grp[g];
         q.x = ps[g].x;
@@ -2098,9 +2004,41 @@ void fill_fwd(ReduceArgs& a, const gm_bn_fwd* ps, int G, bool grouped, const Pla
         q.yout = static_cast<uint4*>(ps[g].y);
         q.mask_out = static_cast<uint8_t*>(ps[g].relu_mask);
     }
-    BnGroup& q = a.grp[0];  // the single-group fields (host bookkeeping only: kernels read grp[])
-    a.x = q.x; a.gamma = q.gamma; a.beta = q.beta; a.rmean = q.rmean; a.rvar = q.rvar;
-    a.save_mean = q.save_mean; a.save_invstd = q.save_invstd; a.nbt = q.nbt; a.coef_out = q.coef_out;
+}
+
+void bwd_groups(ReduceArgs& a, const gm_bn_bwd* ps, int G) {
+    for (int g = 0; g < G; ++g) {
+        BnGroup& q = a.grp[g];
+        q.x = ps[g].x; q.dy = ps[g].dy; q.y = ps[g].y;
+        q.gamma = ps[g].gamma;
+        q.save_mean = const_cast<float*>(ps[g].save_mean);
+        q.save_invstd = const_cast<float*>(ps[g].save_invstd);
+        q.dgamma = ps[g].dgamma; q.dbeta = ps[g].dbeta;
+        q.fcoef = ps[g].fwd_coef;
+        q.yout = static_cast<uint4*>(ps[g].dx);
+        q.dres_out = static_cast<uint4*>(ps[g].dres);
+        q.ymask = static_cast<const uint8_t*>(ps[g].relu_mask);
+    }
+}
+
+// shared fields from group 0, per-group pointers into grp[], scratch split per group
+void fill_fwd(ReduceArgs& a, const gm_bn_fwd* ps, int G, bool grouped, const Plan& pl, char* s) {
+    const gm_bn_fwd* p = ps;
+    a.M = p->M; a.C = p->C; a.tpr_log = pl.tpr_log; a.rpb = pl.rpb;
+    a.SW = pl.SW; a.nrc = pl.nrc;
+    a.momentum = p->momentum; a.eps = p->eps;
+    set_scratch(a, pl, s, grouped);
+    fwd_groups(a, ps, G);
+}
+
+// the single-launch form's plan into a (fused_plan chose it): its grid
+dim3 fused_args(ReduceArgs& a, const Plan& fp, char* s, int G) {
+    a.rpb = fp.rpb;
+    a.nrc = fp.nrc;
+    a.gen = reinterpret_cast<unsigned*>(s) + kGenOff;
+    a.spin_limit = spin_limit();
+    a.redundant = redundant_ok(a.nrc);
+    return dim3(fp.nrc, fp.nslice, G);
 }
 
 template <typename E>
@@ -2116,46 +2054,36 @@ int bn_fwd_train(const gm_bn_fwd* ps, int G, bool grouped, void* scratch, size_t
     ReduceArgs a{};
     fill_fwd(a, ps, G, grouped, pl, s);
     hipStream_t st = as_stream(stream);
-    Plan fp;
-    const int nr = std::is_same<E, uint16_t>::value ? fused_plan(p->M, p->C, fp, false, G) : 0;
-    if (nr) {
-        a.rpb = fp.rpb;
-        a.nrc = fp.nrc;
-        a.gen = reinterpret_cast<unsigned*>(s) + kGenOff;
-        a.spin_limit = spin_limit();
-        a.redundant = redundant_ok(a.nrc);
-        const dim3 g(fp.nrc, fp.nslice, G);
-        const bool res = p->residual != nullptr, relu = p->relu != 0;
+    const dim3 rg(pl.nrc, pl.nslice, G);
+    if constexpr (std::is_same<E, float>::value) {  // reference precision: fp64 accumulation
+        hipLaunchKernelGGL((k_bn_reduce_f64<FWD>), rg, dim3(kT), 0, st, a);
+    } else {
+        Plan fp;
+        const int nr = fused_plan(p->M, p->C, fp, false, G);
+        if (nr) {
+            const dim3 g = fused_args(a, fp, s, G);
+            const bool res = p->residual != nullptr, relu = p->relu != 0;
 #define GM_BN_FUSED_LAUNCH(NR)                                                                        \
     if (res && relu) hipLaunchKernelGGL((k_bn_fwd_fused<true, true, NR>), g, dim3(kT), 0, st, a);     \
     else if (res) hipLaunchKernelGGL((k_bn_fwd_fused<true, false, NR>), g, dim3(kT), 0, st, a);       \
     else if (relu) hipLaunchKernelGGL((k_bn_fwd_fused<false, true, NR>), g, dim3(kT), 0, st, a);      \
     else hipLaunchKernelGGL((k_bn_fwd_fused<false, false, NR>), g, dim3(kT), 0, st, a);
-        if (nr < 0) { GM_BN_FUSED_LAUNCH(0) }
-        else if (nr == 4) { GM_BN_FUSED_LAUNCH(4) }
-        else if (nr == 8) { GM_BN_FUSED_LAUNCH(8) }
-        else { GM_BN_FUSED_LAUNCH(16) }
+            if (nr < 0) { GM_BN_FUSED_LAUNCH(0) }
+            else if (nr == 4) { GM_BN_FUSED_LAUNCH(4) }
+            else if (nr == 8) { GM_BN_FUSED_LAUNCH(8) }
+            else { GM_BN_FUSED_LAUNCH(16) }
 #undef GM_BN_FUSED_LAUNCH
-        return check_launch("k_bn_fwd_fused");
+            return check_launch("k_bn_fwd_fused");
+        }
+        hipLaunchKernelGGL((k_bn_reduce<FWD, E>), rg, dim3(kT), 0, st, a);
     }
-    const dim3 rg(pl.nrc, pl.nslice, G);
-    if (std::is_same<E, float>::value) hipLaunchKernelGGL((k_bn_reduce_f64<FWD>), rg, dim3(kT), 0, st, a);
-    else hipLaunchKernelGGL((k_bn_reduce<FWD, E>), rg, dim3(kT), 0, st, a);
     if ((rc = check_launch("k_bn_reduce<fwd>"))) return rc;
     for (int gi = 0; gi < G; ++gi) {  // the apply: one launch per group
-        ApplyArgs b{};
-        b.nvec = p->M * (p->C / 8); b.tpr_log = ilog2(p->C / 8); b.C = p->C; b.relu = p->relu;
+        ApplyArgs b = apply_args(p->M, p->C, p->relu);
         b.x = ps[gi].x; b.res = ps[gi].residual; b.out = ps[gi].y;
         b.mask_out = static_cast<uint8_t*>(ps[gi].relu_mask);
         b.coef = reinterpret_cast<float*>(reinterpret_cast<char*>(a.coef) + gi * a.scr_stride);
-        const int g = apply_grid(b.nvec, p->C);
-        if (p->residual) {
-            if (p->relu) hipLaunchKernelGGL((k_bn_apply<true, true, E>), dim3(g), dim3(kT), 0, st, b);
-            else hipLaunchKernelGGL((k_bn_apply<true, false, E>), dim3(g), dim3(kT), 0, st, b);
-        } else {
-            if (p->relu) hipLaunchKernelGGL((k_bn_apply<false, true, E>), dim3(g), dim3(kT), 0, st, b);
-            else hipLaunchKernelGGL((k_bn_apply<false, false, E>), dim3(g), dim3(kT), 0, st, b);
-        }
+        launch_apply<E>(p->residual, p->relu, false, dim3(apply_grid(b.nvec)), st, b);
         if ((rc = check_launch("k_bn_apply"))) return rc;
     }
     return GM_OK;
@@ -2173,17 +2101,9 @@ int bn_fwd_infer(const gm_bn_fwd* p, void* scratch, size_t bytes, void* stream, 
     hipLaunchKernelGGL(k_bn_infer_coef, dim3((p->C + 255) / 256), dim3(256), 0, st, p->C, p->gamma, p->beta,
                        p->running_mean, p->running_var, p->eps, coef);
     if ((rc = check_launch("k_bn_infer_coef"))) return rc;
-    ApplyArgs b{};
-    b.nvec = p->M * (p->C / 8); b.tpr_log = ilog2(p->C / 8); b.C = p->C; b.relu = p->relu;
+    ApplyArgs b = apply_args(p->M, p->C, p->relu);
     b.x = p->x; b.res = p->residual; b.out = p->y; b.coef = coef;
-    const int g = apply_grid(b.nvec, p->C);
-    if (p->residual) {
-        if (p->relu) hipLaunchKernelGGL((k_bn_apply<true, true, E>), dim3(g), dim3(kT), 0, st, b);
-        else hipLaunchKernelGGL((k_bn_apply<true, false, E>), dim3(g), dim3(kT), 0, st, b);
-    } else {
-        if (p->relu) hipLaunchKernelGGL((k_bn_apply<false, true, E>), dim3(g), dim3(kT), 0, st, b);
-        else hipLaunchKernelGGL((k_bn_apply<false, false, E>), dim3(g), dim3(kT), 0, st, b);
-    }
+    launch_apply<E>(p->residual, p->relu, false, dim3(apply_grid(b.nvec)), st, b);
     return check_launch("k_bn_apply");
 }
 
@@ -2201,30 +2121,19 @@ int bn_bwd(const gm_bn_bwd* ps, int G, bool grouped, void* scratch, size_t bytes
     a.SW = pl.SW; a.nrc = pl.nrc;
     a.accumulate = p->accumulate;
     set_scratch(a, pl, s, grouped);
-    for (int g = 0; g < G; ++g) {
-        BnGroup& q = a.grp[g];
-        q.x = ps[g].x; q.dy = ps[g].dy; q.y = ps[g].y;
-        q.gamma = ps[g].gamma;
-        q.save_mean = const_cast<float*>(ps[g].save_mean);
-        q.save_invstd = const_cast<float*>(ps[g].save_invstd);
-        q.dgamma = ps[g].dgamma; q.dbeta = ps[g].dbeta;
-        q.fcoef = ps[g].fwd_coef;
-        q.yout = static_cast<uint4*>(ps[g].dx);
-        q.dres_out = static_cast<uint4*>(ps[g].dres);
-        q.ymask = static_cast<const uint8_t*>(ps[g].relu_mask);
-    }
+    bwd_groups(a, ps, G);
     hipStream_t st = as_stream(stream);
-    Plan fp;
-    const int nr = (std::is_same<E, uint16_t>::value && (!p->dres || p->relu)) ? fused_plan(p->M, p->C, fp, true, G)
-                                                                               : 0;
-    if (nr) {
-        a.rpb = fp.rpb;
-        a.nrc = fp.nrc;
-        a.gen = reinterpret_cast<unsigned*>(s) + kGenOff;
-        a.spin_limit = spin_limit();
-        a.redundant = redundant_ok(a.nrc);
-        const dim3 g(fp.nrc, fp.nslice, G);
-        const bool ym = p->relu && p->relu_mask && !maskx;  // the forward's mask bytes in place of y
+    const dim3 rg(pl.nrc, pl.nslice, G);
+    if constexpr (std::is_same<E, float>::value) {  // reference precision: fp64 accumulation
+        if (maskx) hipLaunchKernelGGL((k_bn_reduce_f64<BWD_RELUX>), rg, dim3(kT), 0, st, a);
+        else if (p->relu) hipLaunchKernelGGL((k_bn_reduce_f64<BWD_RELU>), rg, dim3(kT), 0, st, a);
+        else hipLaunchKernelGGL((k_bn_reduce_f64<BWD>), rg, dim3(kT), 0, st, a);
+    } else {
+        Plan fp;
+        const int nr = (!p->dres || p->relu) ? fused_plan(p->M, p->C, fp, true, G) : 0;
+        if (nr) {
+            const dim3 g = fused_args(a, fp, s, G);
+            const bool ym = p->relu && p->relu_mask && !maskx;  // the forward's mask bytes in place of y
 #define GM_BN_BWD_FUSED_LAUNCH(NR)                                                                                  \
     if (maskx) hipLaunchKernelGGL((k_bn_bwd_fused<BWD_RELUX, false, NR>), g, dim3(kT), 0, st, a);                   \
     else if (ym && p->dres) hipLaunchKernelGGL((k_bn_bwd_fused<BWD_RELU, true, NR, true>), g, dim3(kT), 0, st, a);  \
@@ -2232,39 +2141,25 @@ int bn_bwd(const gm_bn_bwd* ps, int G, bool grouped, void* scratch, size_t bytes
     else if (p->relu && p->dres) hipLaunchKernelGGL((k_bn_bwd_fused<BWD_RELU, true, NR>), g, dim3(kT), 0, st, a);   \
     else if (p->relu) hipLaunchKernelGGL((k_bn_bwd_fused<BWD_RELU, false, NR>), g, dim3(kT), 0, st, a);             \
     else hipLaunchKernelGGL((k_bn_bwd_fused<BWD, false, NR>), g, dim3(kT), 0, st, a);
-        if (nr < 0) { GM_BN_BWD_FUSED_LAUNCH(0) }
-        else if (nr == 4) { GM_BN_BWD_FUSED_LAUNCH(4) }
-        else { GM_BN_BWD_FUSED_LAUNCH(8) }
+            if (nr < 0) { GM_BN_BWD_FUSED_LAUNCH(0) }
+            else if (nr == 4) { GM_BN_BWD_FUSED_LAUNCH(4) }
+            else { GM_BN_BWD_FUSED_LAUNCH(8) }
 #undef GM_BN_BWD_FUSED_LAUNCH
-        return check_launch("k_bn_bwd_fused");
+            return check_launch("k_bn_bwd_fused");
+        }
+        if (maskx) hipLaunchKernelGGL((k_bn_reduce<BWD_RELUX, E>), rg, dim3(kT), 0, st, a);
+        else if (p->relu) hipLaunchKernelGGL((k_bn_reduce<BWD_RELU, E>), rg, dim3(kT), 0, st, a);
+        else hipLaunchKernelGGL((k_bn_reduce<BWD, E>), rg, dim3(kT), 0, st, a);
     }
-    const dim3 rg(pl.nrc, pl.nslice, G);
-    if (std::is_same<E, float>::value) {  // reference precision: fp64 accumulation
-        if (maskx) hipLaunchKernelGGL((k_bn_reduce_f64<BWD_RELUX>), rg, dim3(kT), 0, st, a);
-        else if (p->relu) hipLaunchKernelGGL((k_bn_reduce_f64<BWD_RELU>), rg, dim3(kT), 0, st, a);
-        else hipLaunchKernelGGL((k_bn_reduce_f64<BWD>), rg, dim3(kT), 0, st, a);
-    } else if (maskx) hipLaunchKernelGGL((k_bn_reduce<BWD_RELUX, E>), rg, dim3(kT), 0, st, a);
-    else if (p->relu) hipLaunchKernelGGL((k_bn_reduce<BWD_RELU, E>), rg, dim3(kT), 0, st, a);
-    else hipLaunchKernelGGL((k_bn_reduce<BWD, E>), rg, dim3(kT), 0, st, a);
     if ((rc = check_launch("k_bn_reduce<bwd>"))) return rc;
     for (int gi = 0; gi < G; ++gi) {  // the apply: one launch per group
         const gm_bn_bwd* q = ps + gi;
-        ApplyArgs b{};
-        b.nvec = p->M * (p->C / 8); b.tpr_log = ilog2(p->C / 8); b.C = p->C; b.relu = p->relu;
+        ApplyArgs b = apply_args(p->M, p->C, p->relu);
         b.x = q->x; b.res = q->y; b.dy = q->dy; b.out = q->dx;
         b.out2 = q->dres;
         b.coef = reinterpret_cast<float*>(reinterpret_cast<char*>(a.coef) + gi * a.scr_stride);
         b.fcoef = q->fwd_coef;
-        const int g = apply_grid(b.nvec, p->C);
-        if (maskx) {
-            hipLaunchKernelGGL((k_bn_apply_bwd<true, false, true, E>), dim3(g), dim3(kT), 0, st, b);
-        } else if (p->relu) {
-            if (p->dres) hipLaunchKernelGGL((k_bn_apply_bwd<true, true, false, E>), dim3(g), dim3(kT), 0, st, b);
-            else hipLaunchKernelGGL((k_bn_apply_bwd<true, false, false, E>), dim3(g), dim3(kT), 0, st, b);
-        } else {
-            if (p->dres) hipLaunchKernelGGL((k_bn_apply_bwd<false, true, false, E>), dim3(g), dim3(kT), 0, st, b);
-            else hipLaunchKernelGGL((k_bn_apply_bwd<false, false, false, E>), dim3(g), dim3(kT), 0, st, b);
-        }
+        launch_apply_bwd<E>(p->relu, p->dres, maskx, dim3(apply_grid(b.nvec)), st, b);
         if ((rc = check_launch("k_bn_apply_bwd"))) return rc;
     }
     return GM_OK;
@@ -2313,7 +2208,7 @@ extern "C" int gm_bn_set_fused_mode(int mode) {
 // What the planner picks for a bf16 training launch of G groups of [M, C] under the mode,
 // concurrency and residency in effect: fused_plan's own return value.  Read-only.
 extern "C" int gm_bn_fused_form(long long M, int C, int bwd, int G) {
-    if (M <= 0 || C < 8 || C > kMaxC || (C & (C - 1)) != 0 || G < 1 || G > kMaxBnG) return 0;
+    if (!shape_ok(M, C) || G < 1 || G > kMaxBnG) return 0;
     Plan fp;
     return fused_plan(M, C, fp, bwd != 0, G);
 }
@@ -2321,7 +2216,7 @@ extern "C" int gm_bn_fused_form(long long M, int C, int bwd, int G) {
 // Rows per workgroup of that launch (the fused plan's, or make_plan's on the two-launch path):
 // a thread sums rows / (256 / min(C, 64) * 8) of them in fp32, then the row groups are summed.
 extern "C" long long gm_bn_plan_rows(long long M, int C, int bwd, int G) {
-    if (M <= 0 || C < 8 || C > kMaxC || (C & (C - 1)) != 0 || G < 1 || G > kMaxBnG) return 0;
+    if (!shape_ok(M, C) || G < 1 || G > kMaxBnG) return 0;
     Plan fp;
     return fused_plan(M, C, fp, bwd != 0, G) ? fp.rpb : make_plan(M, C).rpb;
 }
@@ -2403,16 +2298,7 @@ static int stem_pool_bwd(const gm_pool_desc* d, int G, const void* dy_pool, cons
     a.M = ps[0].M; a.C = ps[0].C; a.relu = 1; a.SW = ps[0].C; a.tpr_log = 3;
     a.accumulate = ps[0].accumulate;
     set_scratch(a, pl, static_cast<char*>(scratch), true);
-    for (int g = 0; g < G; ++g) {
-        BnGroup& q = a.grp[g];
-        q.x = ps[g].x;
-        q.gamma = ps[g].gamma;
-        q.save_mean = const_cast<float*>(ps[g].save_mean);
-        q.save_invstd = const_cast<float*>(ps[g].save_invstd);
-        q.dgamma = ps[g].dgamma; q.dbeta = ps[g].dbeta;
-        q.fcoef = ps[g].fwd_coef;
-        q.yout = static_cast<uint4*>(ps[g].dx);
-    }
+    bwd_groups(a, ps, G);  // (dy, y, dres, relu_mask: unused by k_stem_pool_bn_bwd)
     StemPoolGeo pg;
     pg.Ng = d->N; pg.H = d->H; pg.W = d->W; pg.P = P; pg.Q = Q;
     pg.items = (long long)d->N * P * Q * (d->C / 8);
@@ -2466,18 +2352,7 @@ static void fwd_stats_args(gm::ReduceArgs& a, const gm_bn_fwd* ps, int G, float*
     a.coef = stats + (size_t)rows * 2 * C;
     a.scr_stride = (unsigned long long)(rows + 1) * 2 * C * sizeof(float);
     a.hdr_words = 0;
-    for (int g = 0; g < G; ++g) {
-        gm::BnGroup& q = a.grp[g];
-        q.x = ps[g].x;
-        q.gamma = ps[g].gamma; q.beta = ps[g].beta;
-        q.rmean = ps[g].running_mean; q.rvar = ps[g].running_var;
-        q.save_mean = ps[g].save_mean; q.save_invstd = ps[g].save_invstd;
-        q.nbt = ps[g].num_batches_tracked;
-        q.coef_out = ps[g].coef_out;
-        q.res = static_cast<const uint4*>(ps[g].residual);
-        q.yout = static_cast<uint4*>(ps[g].y);
-        q.mask_out = static_cast<uint8_t*>(ps[g].relu_mask);
-    }
+    fwd_groups(a, ps, G);
 }
 
 static void bwd_stats_args(gm::ReduceArgs& a, const gm_bn_bwd* ps, int G, float* stats, int rows) {
@@ -2488,16 +2363,7 @@ static void bwd_stats_args(gm::ReduceArgs& a, const gm_bn_bwd* ps, int G, float*
     a.coef = stats;
     a.scr_stride = (unsigned long long)(rows + 1) * 2 * C * sizeof(float);
     a.hdr_words = 0;
-    for (int g = 0; g < G; ++g) {
-        gm::BnGroup& q = a.grp[g];
-        q.x = ps[g].x; q.dy = ps[g].dy;
-        q.gamma = ps[g].gamma;
-        q.save_mean = const_cast<float*>(ps[g].save_mean);
-        q.save_invstd = const_cast<float*>(ps[g].save_invstd);
-        q.dgamma = ps[g].dgamma; q.dbeta = ps[g].dbeta;
-        q.fcoef = ps[g].fwd_coef;
-        q.yout = static_cast<uint4*>(ps[g].dx);
-    }
+    bwd_groups(a, ps, G);  // (y, dres, relu_mask: unused by the kernels from producer statistics)
 }
 
 // BatchNorm forward statistics from producer partial rows (gm_conv2d_fwd_grouped_bn_stats_bf16,
@@ -2509,7 +2375,7 @@ extern "C" int gm_bn_fwd_stats_finalize_grouped(const gm_bn_fwd* ps, int G, floa
     int rc = check_groups_fwd(ps, G, fn);
     if (rc) return rc;
     const int C = ps[0].C;
-    GM_REQUIRE(stats && rows >= 1 && C >= 64 && C % 64 == 0 && ps[0].M >= 1, "%s: C a multiple of 64, rows >= 1",
+    GM_REQUIRE(stats_shape_ok(stats, rows, C) && ps[0].M >= 1, "%s: C a multiple of 64, rows >= 1",
                fn);
     ReduceArgs a{};
     fwd_stats_args(a, ps, G, stats, rows);
@@ -2527,7 +2393,7 @@ static int fwd_apply(const gm_bn_fwd* ps, int G, const float* stats, int rows, c
     if (rc) return rc;
     const gm_bn_fwd* p = ps;
     const int C = p->C;
-    GM_REQUIRE(stats && rows >= 1 && C >= 64 && C % 64 == 0 && p->y, "%s: C a multiple of 64, rows >= 1, y", fn);
+    GM_REQUIRE(stats_shape_ok(stats, rows, C) && p->y, "%s: C a multiple of 64, rows >= 1, y", fn);
     const long long gs = p->M * C;  // elements
     bool strided = true;
     for (int g = 1; g < G; ++g) {
@@ -2541,27 +2407,18 @@ static int fwd_apply(const gm_bn_fwd* ps, int G, const float* stats, int rows, c
     hipStream_t st = as_stream(stream);
     const int ng = strided ? 1 : G;
     for (int gi = 0; gi < ng; ++gi) {
-        ApplyArgs b{};
-        b.nvec = p->M * (C / 8); b.tpr_log = ilog2(C / 8); b.C = C; b.relu = p->relu;
+        ApplyArgs b = apply_args(p->M, C, p->relu);
         b.x = ps[gi].x; b.res = ps[gi].residual; b.out = ps[gi].y;
         b.mask_out = static_cast<uint8_t*>(ps[gi].relu_mask);
         b.coef = stats + gi * cgs + (size_t)rows * 2 * C;
         b.gvec = strided ? gs / 8 : 0;
         b.cgs = strided ? cgs : 0;
-        const dim3 g(apply_grid(b.nvec, C), strided ? G : 1);
         if (rstats) {
             const long long rcgs = (long long)(rrows + 1) * 2 * C;
             b.rcoef = rstats + gi * rcgs + (size_t)rrows * 2 * C;
             b.rcgs = strided ? rcgs : 0;
-            if (p->relu) hipLaunchKernelGGL((k_bn_apply<true, true, uint16_t, true>), g, dim3(kT), 0, st, b);
-            else hipLaunchKernelGGL((k_bn_apply<true, false, uint16_t, true>), g, dim3(kT), 0, st, b);
-        } else if (p->residual) {
-            if (p->relu) hipLaunchKernelGGL((k_bn_apply<true, true, uint16_t>), g, dim3(kT), 0, st, b);
-            else hipLaunchKernelGGL((k_bn_apply<true, false, uint16_t>), g, dim3(kT), 0, st, b);
-        } else {
-            if (p->relu) hipLaunchKernelGGL((k_bn_apply<false, true, uint16_t>), g, dim3(kT), 0, st, b);
-            else hipLaunchKernelGGL((k_bn_apply<false, false, uint16_t>), g, dim3(kT), 0, st, b);
         }
+        launch_apply<uint16_t>(p->residual, p->relu, rstats != nullptr, dim3(apply_grid(b.nvec), strided ? G : 1), st, b);
         if ((rc = check_launch("k_bn_apply"))) return rc;
     }
     return GM_OK;
@@ -2583,7 +2440,7 @@ static int check_bwd_from_stats(const gm_bn_bwd* ps, int G, const float* stats, 
     int rc = check_groups_bwd(ps, G, fn);
     if (rc) return rc;
     const int C = ps[0].C;
-    GM_REQUIRE(stats && rows >= 1 && C >= 64 && C % 64 == 0 && ps[0].M >= 1, "%s: C a multiple of 64, rows >= 1",
+    GM_REQUIRE(stats_shape_ok(stats, rows, C) && ps[0].M >= 1, "%s: C a multiple of 64, rows >= 1",
                fn);
     GM_REQUIRE(!ps[0].dres && (!ps[0].relu || ps[0].fwd_coef),
                "%s: relu needs fwd_coef (mask from x); no residual gradient", fn);
@@ -2621,17 +2478,15 @@ extern "C" int gm_bn_bwd_apply_grouped_bf16(const gm_bn_bwd* ps, int G, const fl
     hipStream_t st = as_stream(stream);
     const int ng = strided ? 1 : G;
     for (int gi = 0; gi < ng; ++gi) {
-        ApplyArgs b{};
-        b.nvec = p->M * (C / 8); b.tpr_log = ilog2(C / 8); b.C = C; b.relu = p->relu;
+        ApplyArgs b = apply_args(p->M, C, p->relu);
         b.x = ps[gi].x; b.dy = ps[gi].dy; b.out = ps[gi].dx;
         b.coef = coef0 + (size_t)gi * 4 * C;
         b.fcoef = ps[gi].fwd_coef;
         b.gvec = strided ? gs / 8 : 0;
         b.cgs = strided ? 4 * C : 0;
         b.fcgs = strided ? 2 * C : 0;
-        const dim3 g(apply_grid(b.nvec, C), strided ? G : 1);
-        if (p->relu) hipLaunchKernelGGL((k_bn_apply_bwd<true, false, true, uint16_t>), g, dim3(kT), 0, st, b);
-        else hipLaunchKernelGGL((k_bn_apply_bwd<false, false, false, uint16_t>), g, dim3(kT), 0, st, b);
+        // (check_bwd_from_stats: relu means the mask from x, and no dres)
+        launch_apply_bwd<uint16_t>(p->relu, false, p->relu, dim3(apply_grid(b.nvec), strided ? G : 1), st, b);
         if ((rc = check_launch("k_bn_apply_bwd"))) return rc;
     }
     return GM_OK;
@@ -2681,7 +2536,7 @@ extern "C" int gm_bn_fwd_finalize_apply_grouped_bf16_ex(const gm_bn_fwd* ps, int
     int rc = check_groups_fwd(ps, G, fn);
     if (rc) return rc;
     const int C = ps[0].C;
-    GM_REQUIRE(stats && rows >= 1 && C >= 64 && C % 64 == 0 && ps[0].M >= 1 && ps[0].y,
+    GM_REQUIRE(stats_shape_ok(stats, rows, C) && ps[0].M >= 1 && ps[0].y,
                "%s: C a multiple of 64, rows >= 1, y", fn);
     for (int g = 0; g < G; ++g)
         GM_REQUIRE(!ps[g].relu_mask == !ps[0].relu_mask, "%s: relu_mask in all groups or none", fn);
@@ -2718,7 +2573,7 @@ extern "C" int gm_bn_fwd_finalize_apply_res_affine_grouped_bf16_ex(const gm_bn_f
     int rc = check_groups_fwd(ps, G, fn);
     if (rc || (rc = check_groups_fwd(rps, G, fn))) return rc;
     const int C = ps[0].C;
-    GM_REQUIRE(stats && rstats && rows >= 1 && rrows >= 1 && C >= 64 && C % 64 == 0 && ps[0].M >= 1 && ps[0].y,
+    GM_REQUIRE(stats_shape_ok(stats, rows, C) && stats_shape_ok(rstats, rrows, C) && ps[0].M >= 1 && ps[0].y,
                "%s: C a multiple of 64, rows >= 1, y", fn);
     for (int g = 0; g < G; ++g) {
         GM_REQUIRE(!ps[g].relu_mask == !ps[0].relu_mask, "%s: relu_mask in all groups or none", fn);

@@ -9,7 +9,8 @@ GMBatchNorm2d in fp32 (fp64 sums, centred backward coefficients), the stem's fus
 BatchNorm + ReLU + max-pool, the grouped launches of vtrunk.vbn and of the stem's pool-gathering
 backward with two view groups of different statistics, and eval mode (gm_bn_fwd_infer_*,
 gm_bn_infer_coef) on running statistics with a tiny and an exactly zero variance.  Forms: plain,
-ReLU with the mask recomputed from x and read from y, residual + ReLU.  Checked: y, save_mean,
+ReLU with the mask recomputed from x and read from y, residual + ReLU, and (GMBatchNorm2d only: the
+form whose kernels nothing else launches) a residual without ReLU.  Checked: y, save_mean,
 save_invstd, running statistics (momentum 1 in the plain form, 0.1 in the others),
 num_batches_tracked, dx, dres, dgamma, dbeta - with the bounds derived in bnregimes.py and never
 fitted.  K = 16 + the fp32 addition chain of the launch's plan (gm_bn_plan_rows) for every bf16
@@ -118,14 +119,14 @@ def variant(form):
 ORDER = [4, 8, 16, -1]   # the forms in the order a growing map passes through them
 
 
-def smallest_m(bwd, target):
-    """Smallest M at C = 64 whose forward (backward) the planner gives the form `target` (mode 2,
-    concurrency and residency as they are): rows per thread grow with M, so the forms follow one
-    another in ORDER and bisection finds where `target` begins."""
-    key = f"{'bwd' if bwd else 'fwd'} {variant(target)}"
+def smallest_m(bwd, target, G=1):
+    """Smallest M at C = 64 whose forward (backward) the planner gives the form `target` for a launch
+    of G view groups (mode 2, concurrency and residency as they are): rows per thread grow with M, so
+    the forms follow one another in ORDER and bisection finds where `target` begins."""
+    key = f"{'bwd' if bwd else 'fwd'} {variant(target)}" + (f" G={G}" if G > 1 else "")
     if key not in FOUND:
         _, lib = _lib()
-        form = lambda m: lib.gm_bn_fused_form(m, 64, int(bwd), 1)  # noqa: E731
+        form = lambda m: lib.gm_bn_fused_form(m, 64, int(bwd), G)  # noqa: E731
         reached = lambda m: form(m) in ORDER and ORDER.index(form(m)) >= ORDER.index(target)  # noqa: E731
         lo, hi = 1, 1 << 21
         assert form(hi) == -1, f"the planner never streams at C = 64 (form {form(hi)} at M = {hi})"
@@ -148,15 +149,19 @@ def _module(c, dtype, momentum):
     return m
 
 
-def _train_case(shape, form, dtype, path, expect=None):
+def _train_case(shape, form, dtype, path, expect=None, bwd_two_kernel=False):
     """One GMBatchNorm2d forward + backward against the reference; expect(ff, fb): the variant
-    assertion of the row.  Returns the forms reached."""
+    assertion of the row.  bwd_two_kernel: the backward takes the two launches whatever the planner
+    answers (a residual gradient without ReLU), so its K is the two-launch plan's.  Returns the
+    forms reached."""
     from greedy_multimodal_learning_amd import bn as B
     name, relu, res, maskx = form
     c = case(shape)
     bf16 = dtype == BF
     momentum = 1.0 if name == "plain" else 0.1
     ff, fb, kf, kb = plan(c.M, c.C) if bf16 else (0, 0, 16, 16)
+    if bwd_two_kernel and bf16:
+        fb, kb = 0, 16 + R.chain(R.two_kernel_rows(c.M, c.C)[0], c.C)
     if expect is not None:
         expect(ff, fb)
     x, dy, r, *_ = R.device_inputs(c, DEV, dtype)
@@ -246,6 +251,31 @@ def test_bn_f32(shape, form):
     _train_case(shape, form, F32, "GMBatchNorm2d fp32")
 
 
+# ---- 2b. a residual without ReLU ---------------------------------------------------------------
+
+RES_PLAIN = ("res_plain", False, True, True)
+
+
+@pytest.mark.parametrize("target", [0, 4, 8, 16, -1, "fp32"],
+                         ids=["two-kernel", "NR4", "NR8", "NR16", "streaming", "fp32"])
+def test_bn_residual_without_relu(target, fused_mode):
+    """y = x sc + sh + r with no ReLU: no ResNet block has the form and no other row launches its
+    kernels - k_bn_apply<RES, no RELU> in bf16 and fp32, k_bn_fwd_fused<RES, no RELU, NR> at every
+    NR (the smallest map that takes each, as the larger-variants rows) and k_bn_apply_bwd<no RELU,
+    DRES> in bf16 and fp32: the backward of a residual gradient without ReLU is always the two
+    launches - read from the dispatch code (bn_bwd in csrc/batchnorm.hip: the planner is not asked
+    when dres && !relu), not observed here - so its K is the two-launch plan's."""
+    if target == "fp32":
+        _train_case((7, 64, 9, 11), RES_PLAIN, F32, "GMBatchNorm2d fp32")
+        return
+    fused_mode(0 if target == 0 else 2)
+    shape = (7, 64, 9, 11) if target in (0, 4) else (1, 64, 1, smallest_m(False, target))
+
+    def expect(ff, fb):
+        assert ff == target, f"{shape}: forward form {ff}, wanted {target}"
+    _train_case(shape, RES_PLAIN, BF, "GMBatchNorm2d bf16", expect, bwd_two_kernel=True)
+
+
 # ---- 3. the stem's fused BatchNorm + ReLU + max-pool -------------------------------------------
 
 def _pooled_dy(c, idx):
@@ -328,6 +358,48 @@ def test_vbn_two_groups(mode, shape, form, fused_mode, monkeypatch):
                                     dres=R.rows(RS.grad[sl]) if res else None,
                                     dgamma=bns[g].weight.grad.double().cpu(), dbeta=bns[g].bias.grad.double().cpu()))
         note("vtrunk.vbn G=2", f"forward {variant(ff)}, backward {variant(fb)}", out)
+
+
+@pytest.mark.parametrize("dres", [True, False], ids=["dres", "nodres"])
+@pytest.mark.parametrize("target", [4, 8, -1], ids=["bwd-NR4", "bwd-NR8", "bwd-streaming"])
+def test_vbn_mask_byte_backward(target, dres, fused_mode, monkeypatch):
+    """The backward that reads the forward's ReLU mask bytes in place of y (vtrunk.BN_RELU_MASK:
+    k_bn_bwd_fused<BWD_RELU, DRES, NR, YM>), two view groups, residual + ReLU, at the smallest map
+    whose backward of two groups takes each form - with the residual's gradient (DRES) and, the
+    residual not requiring one, without it.  The row fails if the launch does not take that form
+    or the forward stored no mask."""
+    from greedy_multimodal_learning_amd import vtrunk
+    fused_mode(2)
+    monkeypatch.setattr(vtrunk, "BN_RELU_MASK", True)
+    G = 2
+    shape = (7, 64, 9, 11) if target == 4 else (1, 64, 1, smallest_m(True, target, G))
+    cs = [case(shape, g) for g in range(G)]
+    ff, fb, kf, kb = plan(cs[0].M, cs[0].C, G)
+    assert fb == target, f"M = {cs[0].M}: backward form {fb}, wanted {target}"
+    ins = [R.device_inputs(c, DEV, BF) for c in cs]
+    cat = lambda i: torch.cat([t[i] for t in ins]).contiguous(memory_format=torch.channels_last)  # noqa: E731
+    X = cat(0).requires_grad_(True)
+    RS = cat(2).requires_grad_(dres)
+    bns = _group_modules(shape, G)
+    y = vtrunk.vbn(X, bns, residual=RS, relu=True)
+    sm, si, ymask = y.grad_fn.saved_tensors[2:5]
+    assert ymask is not None and int(ymask.count_nonzero()) > 0, "the forward stored no ReLU mask bytes"
+    y.backward(cat(1))
+    assert (RS.grad is not None) == dres
+    N = shape[0]
+    for g, c in enumerate(cs):
+        sl = slice(g * N, (g + 1) * N)
+        what = f"vbn mask bytes G=2 group {g} {ids(shape)} {'dres' if dres else 'no dres'}"
+        f = fref(shape, g, True, True)
+        wy, mask = R.check_forward(f, R.rows(y[sl]), True, what)
+        out = {"y": wy}
+        out.update(R.check_stats(c, f, kf, 0.1, what, save_mean=sm[g], save_invstd=si[g],
+                                 running_mean=bns[g].running_mean, running_var=bns[g].running_var))
+        b = R.backward_ref(c, f, mask=mask)
+        out.update(R.check_backward(c, b, kb, True, what, dx=R.rows(X.grad[sl]),
+                                    dres=R.rows(RS.grad[sl]) if dres else None,
+                                    dgamma=bns[g].weight.grad.double().cpu(), dbeta=bns[g].bias.grad.double().cpu()))
+        note("vtrunk.vbn G=2 mask bytes", f"backward {variant(fb)}", out)
 
 
 def test_vstem_pool_backward_two_groups():
