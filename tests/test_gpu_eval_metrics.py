@@ -3,7 +3,12 @@ device accumulators - against losses.blend_loss / losses.acc on the same tensors
 
 Counts are integers and must be equal.  The loss sum is a sum of fp32 per-row terms (lse in
 fp32, as gm_xent_fwd) accumulated in fp64; against blend_loss * B recomputed in fp64 the per-row
-fp32 rounding (2^-24 relative on terms of size ~ log N + |logit|) leaves well under rtol 1e-5."""
+fp32 rounding (2^-24 relative on terms of size ~ log N + |logit|) leaves well under rtol 1e-5.
+
+Also every nbranch EvalStep sends here (1 to 8), batches past the 256 threads of the one
+workgroup, NaN logits, and near ties of the branch mean built by endsref.near_tie_logits, on which
+sum / nbranch and sum * (1 / nbranch) pick different classes: the kernel multiplies by the
+reciprocal, and so does torch's device mean behind losses.acc (torch's CPU mean divides)."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -60,6 +65,85 @@ def test_counts_equal_and_loss_close(dev, nb, B):
     assert (n, hit, hits) == (wn, wh, whs)
     assert sum(hits) > 0
     assert abs(loss - wl) <= 1e-5 * abs(wl)
+
+
+@pytest.mark.parametrize("nb", [1, 3, 8])
+@pytest.mark.parametrize("B", [3, 257, 600])
+def test_counts_one_three_eight_branches_and_second_trips(dev, nb, B):
+    """EvalStep sends any nbranch <= 8 here; B = 257 and 600 take the one workgroup's sample loop
+    a second and a third time."""
+    g = torch.Generator().manual_seed(1000 * nb + B)
+    logits = (3 * torch.randn(nb, B, N, generator=g)).to(dev)
+    y = torch.randint(0, N, (B,), generator=g).to(dev)
+    for b in range(0, B, 2):
+        logits[b % nb, b, y[b]] += 12.0
+    loss, n, hit, hits = _read(_metrics(logits, y))
+    wl, wn, wh, whs = _want(logits, y)
+    print(f"nb {nb} B {B}: loss {loss!r} vs {wl!r} (rel {abs(loss - wl) / abs(wl):.3g}); counts {hit} {hits}")
+    assert (n, hit, hits) == (wn, wh, whs)
+    assert len(hits) == nb and sum(hits) > 0
+    if B > 256:
+        assert hit not in (0, B)      # neither all of one trip nor none: the trips' counts add up
+    assert abs(loss - wl) <= 1e-5 * abs(wl)
+
+
+@pytest.mark.parametrize("nb", [1, 3, 4])
+def test_nan_logits_count_as_torch_argmax(dev, nb):
+    """A NaN logit is the maximum and the first NaN wins, in a branch and in the branch mean, as
+    torch.argmax; a label at that index is a hit; the loss sum is NaN."""
+    B = 257
+    g = torch.Generator().manual_seed(50 + nb)
+    logits = 3 * torch.randn(nb, B, N, generator=g)
+    y = torch.randint(0, N, (B,), generator=g)
+    nan = float("nan")
+    want_hit = 0
+    for b in range(B):
+        kind = b % 4                                      # 3: a clean sample
+        c1, c2 = 3 + b % 11, 20 + b % 13                  # c1 < c2
+        if kind == 0:                                     # one NaN, the label on it
+            logits[b % nb, b, c1] = nan
+            y[b] = c1
+        elif kind == 1:                                   # two NaNs (two branches where there are two), label on the first
+            logits[b % nb, b, c2] = nan
+            logits[(b + 1) % nb, b, c1] = nan
+            y[b] = c1
+        elif kind == 2:                                   # two NaNs, label on the second: a miss
+            logits[b % nb, b, c1] = nan
+            logits[(b + 1) % nb, b, c2] = nan
+            y[b] = c2
+        want_hit += kind in (0, 1)
+    logits, y = logits.to(dev), y.to(dev)
+    clean = torch.arange(B, device=dev) % 4 == 3
+    mean_arg = torch.stack([logits[i] for i in range(nb)]).mean(0).argmax(1)
+    want_hit += int((mean_arg[clean] == y[clean]).sum())
+    loss, n, hit, hits = _read(_metrics(logits, y))
+    _, wn, wh, whs = _want(logits, y)
+    assert loss != loss
+    assert (n, hit, hits) == (wn, wh, whs)
+    assert hit == want_hit
+    assert hits == [int((logits[i].argmax(1) == y).sum()) for i in range(nb)]
+
+
+@pytest.mark.parametrize("nb", [3, 5, 6, 7])
+@pytest.mark.parametrize("collapse", ["div", "mul"])
+def test_near_ties_of_the_branch_mean(dev, nb, collapse):
+    """Two class sums that are adjacent floats: sum / nbranch and sum * (1 / nbranch) do not
+    collapse the same pairs to a tie, so the two formulas pick different classes on every sample
+    of these inputs (endsref.near_tie_logits, both directions).  The ensemble count must be
+    losses.acc's on the same device tensors."""
+    import endsref as E
+    B = 257
+    x, y = E.near_tie_logits(nb, B, N, collapse)
+    d, m = E.top1_by(x, nb, E.mean_div), E.top1_by(x, nb, E.mean_mul)
+    assert bool((d != m).all())
+    logits, yd = x.to(dev), y.to(dev)
+    _, n, hit, hits = _read(_metrics(logits, yd))
+    _, wn, wh, whs = _want(logits, yd)
+    by_div, by_mul = int((d == y).sum()), int((m == y).sum())
+    print(f"nb {nb} collapse {collapse}: kernel {hit}, losses.acc on the device {wh}; "
+          f"the division gives {by_div}, the reciprocal multiply {by_mul}")
+    assert by_div != by_mul and wh in (by_div, by_mul)
+    assert (n, hit, hits) == (wn, wh, whs)
 
 
 def test_two_calls_accumulate(dev):

@@ -90,9 +90,12 @@ def test_gemm_outer_product_shapes(dev, M, N, K, acc):
 @pytest.mark.parametrize("layout", ["nchw", "nhwc"])
 @pytest.mark.parametrize("B,C,H,W", [(2, 128, 28, 28), (3, 256, 14, 14), (64, 512, 7, 7),
                                      (1, 8, 1, 1), (5, 64, 3, 5), (7, 128, 1, 3),
-                                     (3, 2048, 7, 7), (2, 4096, 2, 3)])  # ResNet-50 widths: several channel slabs
+                                     (3, 2048, 7, 7), (2, 4096, 2, 3),   # ResNet-50 widths: several channel slabs
+                                     (9, 4096, 2, 3)])  # 36,864 NCHW rows: past k_rowreduce_nchw's 8192 x 4 waves
 def test_spatial_reduce_and_scale(dev, dtype, layout, B, C, H, W):
     from greedy_multimodal_learning_amd import ops, _lib as L
+    if (B, C) == (9, 4096):
+        assert B * C > ROWS_CAP and 64 * 512 == ROWS_CAP   # the largest other shape stops at the cap
     g = torch.Generator().manual_seed(B * C + H)
     x = torch.randn(B, C, H, W, generator=g).to(dtype)
     dy = torch.randn(B, C, H, W, generator=g).to(dtype)
@@ -132,6 +135,70 @@ def test_spatial_reduce_and_scale(dev, dtype, layout, B, C, H, W):
     ops.channel_scale([dict(x=X, y=Y, C=C, HW=HW, s=S, ld_s=0)], B, dt, lay, dev)
     ref_b = (xf * s.double()[0][None, :, None, None]).to(dtype).double()
     np.testing.assert_allclose(Y.cpu().double().numpy(), ref_b.numpy(), rtol=tol, atol=tol)
+
+
+SCALE_CAP = 16384 * 256   # channel_scale_impl's grid cap: the vectors one trip of k_channel_scale covers
+ROWS_CAP = 8192 * 4       # launch_rows' grid cap: the rows one trip of k_rowreduce_nchw covers
+
+
+@pytest.mark.parametrize("layout", ["nchw", "nhwc"])
+@pytest.mark.parametrize("dtype,shape,vec", [(torch.bfloat16, (5, 2048, 58, 57), 8),
+                                             (torch.float32, (5, 1024, 58, 57), 4),
+                                             (torch.bfloat16, (3, 1031, 37, 37), 1),
+                                             (torch.float32, (3, 1031, 37, 37), 1)],
+                         ids=["bf16x8", "f32x4", "bf16x1", "f32x1"])
+def test_channel_scale_second_trip(dev, dtype, shape, vec, layout):
+    """k_channel_scale strides over a grid capped at 16384 x 256 vectors; the largest map elsewhere
+    in the suite has about 0.4 M.  Each case exceeds the cap in vectors of `vec` elements (an odd
+    element count forces the one-element form; HW % vec != 0 the NCHW form that looks up the
+    channel per element), with and without the additive term, alone and as problem 0 of a
+    two-problem launch whose problem 1 then starts beyond the first trip.  Reference: the fp64
+    formula of test_spatial_reduce_and_scale, evaluated on the device, at its tolerances."""
+    from greedy_multimodal_learning_amd import ops
+    B, C, H, W = shape
+    HW = H * W
+    numel = B * C * HW
+    assert numel % vec == 0 and numel // vec > SCALE_CAP
+    if vec == 1:
+        assert numel % 2 == 1
+    else:
+        assert HW % vec != 0
+    fmt = torch.channels_last if layout == "nhwc" else torch.contiguous_format
+    g = torch.Generator(device=dev).manual_seed(B * C + H)
+
+    def make(shp):
+        x = torch.randn(shp, device=dev, generator=g).to(dtype).contiguous(memory_format=fmt)
+        s = torch.rand(shp[0], shp[1], device=dev, generator=g)
+        a = torch.randn(shp[0], shp[1], device=dev, generator=g)
+        return x, s, a
+
+    def ref(x, s, a, hw):
+        r = x.double() * s.double()[:, :, None, None]
+        if a is not None:
+            r = r + a.double()[:, :, None, None] / hw
+        return r.to(dtype).double()
+
+    def close(y, r):
+        tol = 1e-6 if dtype == torch.float32 else 8e-3
+        return bool(((y.double() - r).abs() <= tol + tol * r.abs()).all())
+
+    big, small = make(shape), make((B, 64, 3, 5))
+    lay = ops.act_layout(big[0])
+    assert lay == ops.act_layout(small[0])
+    dt = ops._DT[dtype]
+    for add in (False, True):
+        for nprob in (1, 2):
+            probs, outs = [], []
+            for (x, s, a), (c, hw) in list(zip((big, small), ((C, HW), (64, 15))))[:nprob]:
+                y = torch.full_like(x, float("nan"))
+                outs.append((x, s, a if add else None, hw, y))
+                p = dict(x=x, y=y, C=c, HW=hw, s=s, ld_s=c)
+                if add:
+                    p.update(a=a, ld_a=c, alpha=1.0 / hw)
+                probs.append(p)
+            ops.channel_scale(probs, B, dt, lay, dev)
+            for i, (x, s, a, hw, y) in enumerate(outs):
+                assert close(y, ref(x, s, a, hw)), f"add={add} nprob={nprob} problem {i}"
 
 
 def test_running_avg(dev):
