@@ -205,6 +205,24 @@ class GateStateN(ctypes.Structure):
                 ("d_bdr", ctypes.c_double)]
 
 
+LR_MAX_MILESTONES = 8
+
+
+class LrState(ctypes.Structure):
+    """gm_lr_state: the device-resident learning rate and its schedule (lr at offset 0)."""
+    _fields_ = [("lr", c_float), ("kind", c_int), ("step", ctypes.c_longlong), ("base_lr", ctypes.c_double),
+                ("min_lr", ctypes.c_double), ("gamma", ctypes.c_double), ("warmup_start", ctypes.c_double),
+                ("warmup_steps", ctypes.c_longlong), ("total_steps", ctypes.c_longlong),
+                ("n_milestones", c_int), ("pad_", c_int), ("milestones", ctypes.c_longlong * LR_MAX_MILESTONES)]
+
+
+EXPORTS.update({
+    "gm_group_sumsq_lr": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_float, c_void_p, c_float,
+                                  c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "gm_lr_at": (c_int, [c_void_p, ctypes.c_longlong, c_void_p]),
+})
+
+
 class StemPack(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("dtype", c_int), ("N", c_int), ("C0", c_int), ("H", c_int), ("W", c_int),
                 ("pad", c_int), ("sn", ctypes.c_longlong), ("sc", ctypes.c_longlong), ("sh", ctypes.c_longlong),

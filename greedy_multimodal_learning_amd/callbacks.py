@@ -123,6 +123,8 @@ class GroupNorms:
     weight decay launches gm_group_sumsq_sgdm instead: torch.optim.SGD's update
     (dampening 0, no Nesterov term) on caller-owned, zero-initialised momentum buffers,
     with the same sums (the gradient's without the decay term).
+    `sums(..., lr_state=)` launches gm_group_sumsq_lr: the same update in every form, with the
+    rate read from a gm_lr_state in device memory, whose schedule the finalize launch advances.
     """
 
     def __init__(self, named_params, branchnames, MMTMnames):
@@ -182,16 +184,25 @@ class GroupNorms:
             self._out = torch.empty(2 * self.ngroups, dtype=torch.float64, device=self.device)
 
     def sums(self, grad_scale=1.0, lr=0.0, gate=None, gate_n=False, momentum=0.0, weight_decay=0.0,
-             momentum_buffers=None):
+             momentum_buffers=None, lr_state=None):
         """The step's group sums (and the fused SGD when lr != 0); gate (a device gm_gate_state /
         gm_gate_state_n tensor): the on-device gate's step runs in the same finalize launch.
         momentum / weight_decay (either non-zero: gm_group_sumsq_sgdm, whose update runs at
         any lr): torch.optim.SGD's; momentum_buffers: with a non-zero momentum, a list
         parallel to the parameters of zero-initialised fp32 tensors shaped and strided like
-        them (None where the parameter has no gradient), advanced in place."""
+        them (None where the parameter has no gradient), advanced in place.
+        lr_state (a device uint8 tensor holding a gm_lr_state; lr must stay 0): gm_group_sumsq_lr,
+        the update at the state's rate (it always runs) and the state advanced by one pass."""
         L.load()
         if not self.params[0].is_cuda:
             raise L.GreedyMMLError("group norms run on HIP devices only (no CPU fallback)")
+        if lr_state is not None:
+            if lr != 0:
+                raise L.GreedyMMLError("group norms: lr_state and a non-zero lr are two owners of the rate")
+            if (lr_state.dtype != torch.uint8 or lr_state.device != self.device or not lr_state.is_contiguous()
+                    or lr_state.numel() < ctypes.sizeof(L.LrState) or lr_state.data_ptr() % 8):
+                raise L.GreedyMMLError("group norms: lr_state must be a contiguous, 8-byte aligned uint8 tensor "
+                                       "holding a gm_lr_state on the parameters' device")
         self._build()
         out = torch.empty(2 * self.ngroups, dtype=torch.float64, device=self.device)
         sgdm = momentum != 0 or weight_decay != 0
@@ -202,7 +213,11 @@ class GroupNorms:
         lib, table, stream = L.load(), self._table.data_ptr(), L.stream_of(self.device)
         sizes = (len(self.params), self.total, self.ngroups, float(grad_scale), float(lr))
         bufs = (out.data_ptr(), self._scratch.data_ptr(), self._scratch.numel())
-        if sgdm:
+        if lr_state is not None:
+            name = "gm_group_sumsq_lr"
+            rc = lib.gm_group_sumsq_lr(table, mom, *sizes[:4], lr_state.data_ptr(), float(momentum),
+                                       float(weight_decay), *bufs, L.ptr(gate), int(bool(gate_n)), stream)
+        elif sgdm:
             name = "gm_group_sumsq_sgdm"
             rc = lib.gm_group_sumsq_sgdm(table, mom, *sizes, float(momentum), float(weight_decay), *bufs,
                                          L.ptr(gate), int(bool(gate_n)), stream)

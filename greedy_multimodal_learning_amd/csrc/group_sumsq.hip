@@ -16,11 +16,14 @@
 // (stream_segment<upd>), the chunk body per group-count form (chunk_sums, chunk_sums_runs) and
 // the host launch path (group_sumsq).  The update form - none, sgd, decay, mom - is a template
 // parameter all the way down; the eight __global__ kernels and the three entry points are
-// wrappers that choose it.
+// wrappers that choose it.  The device-rate wrappers (k_group_sumsq_dlr, gm_group_sumsq_lr) read
+// the learning rate from a gm_lr_state in device memory instead of an argument, and their
+// finalize advances its schedule (lr_rule.h): one captured step for every rate.
 #include <cmath>
 
 #include "gm_common.h"
 #include "gate_rule.h"
+#include "lr_rule.h"
 
 namespace gm {
 
@@ -280,6 +283,27 @@ __global__ __launch_bounds__(256) void k_group_sumsq_sgdm_runs(const gm_tensor* 
     chunk_sums_runs<MOM ? upd::mom : upd::decay>(tab, mom, nt, total, ngroups, h, chunk, rows);
 }
 
+// The device-rate forms: the rate is *lrs, read once per workgroup (a uniform load that ends in a
+// scalar register as the argument does); otherwise the kernels above, for every update form.
+template <upd U, int MG>
+__global__ __launch_bounds__(256) void k_group_sumsq_dlr(const gm_tensor* __restrict__ tab,
+                                                         float* const* __restrict__ mom, int nt, long long total,
+                                                         int ngroups, float gscale,
+                                                         const gm_lr_state* __restrict__ lrs, float mu, float wd,
+                                                         long long chunk, double* __restrict__ rows) {
+    chunk_sums<U, MG>(tab, mom, nt, total, ngroups, {gscale, lrs->lr, mu, wd}, chunk, rows);
+}
+
+template <upd U>
+__global__ __launch_bounds__(256) void k_group_sumsq_dlr_runs(const gm_tensor* __restrict__ tab,
+                                                              float* const* __restrict__ mom, int nt,
+                                                              long long total, int ngroups, float gscale,
+                                                              const gm_lr_state* __restrict__ lrs, float mu,
+                                                              float wd, long long chunk,
+                                                              double* __restrict__ rows) {
+    chunk_sums_runs<U>(tab, mom, nt, total, ngroups, {gscale, lrs->lr, mu, wd}, chunk, rows);
+}
+
 // 1024 threads stream the [nrows][w] row block as one flat array with fully coalesced
 // 8-byte loads: thread t < S (S = the largest multiple of w <= 1024) owns column t % w and
 // reads elements t, t + S, ... (8 in flight).  The former form gave each thread whole
@@ -289,9 +313,8 @@ __global__ __launch_bounds__(256) void k_group_sumsq_sgdm_runs(const gm_tensor* 
 constexpr int kFinT = 1024;
 // gate (optional): the on-device gate's state - gm_gate_state (gate_n 0) or gm_gate_state_n (1) -
 // whose step rule thread 0 applies to the finished sums (gm_group_sumsq_gate: no gate launch)
-__global__ __launch_bounds__(kFinT) void k_group_finalize(const double* __restrict__ rows, int nrows,
-                                                          int ngroups, double* __restrict__ out,
-                                                          void* gate = nullptr, int gate_n = 0) {
+__device__ __forceinline__ void finalize_sums(const double* __restrict__ rows, int nrows, int ngroups,
+                                              double* __restrict__ out, void* gate, int gate_n) {
     __shared__ double s[kFinT];
     __shared__ double tot_s[2 * kMaxGroups];
     __shared__ double part[32 * 2 * kMaxGroups];
@@ -335,6 +358,21 @@ __global__ __launch_bounds__(kFinT) void k_group_finalize(const double* __restri
     }
 }
 
+__global__ __launch_bounds__(kFinT) void k_group_finalize(const double* __restrict__ rows, int nrows,
+                                                          int ngroups, double* __restrict__ out,
+                                                          void* gate = nullptr, int gate_n = 0) {
+    finalize_sums(rows, nrows, ngroups, out, gate, gate_n);
+}
+
+// The finalize of the device-rate forms: thread 0 also advances the rate's schedule, after the
+// sums and the gate's rule (the pass that read the old rate ended before this launch began)
+__global__ __launch_bounds__(kFinT) void k_group_finalize_lr(const double* __restrict__ rows, int nrows,
+                                                             int ngroups, double* __restrict__ out, void* gate,
+                                                             int gate_n, gm_lr_state* lrs) {
+    finalize_sums(rows, nrows, ngroups, out, gate, gate_n);
+    if (threadIdx.x == 0) lr_advance(lrs);
+}
+
 }  // namespace gm
 
 using namespace gm;
@@ -346,10 +384,16 @@ extern "C" size_t gm_group_sumsq_scratch(long long total) {
 }
 
 // The launch path of every entry point: shared checks, chunking, the kernel of (form, group
-// count), finalize.  mom: the buffers of upd::mom; gate: optional (null: sums only).
+// count), finalize.  mom: the buffers of upd::mom; gate: optional (null: sums only); lrs: the
+// device rate of the device-rate forms (null: h.lr, the argument).
+template <upd U>
+static auto dlr_kernel(bool few) {
+    return few ? k_group_sumsq_dlr<U, 8> : k_group_sumsq_dlr_runs<U>;
+}
+
 static int group_sumsq(const gm_tensor* table, float* const* mom, int nt, long long total, int ngroups,
                        const sgdm_args& h, upd form, double* out, void* scratch, size_t scratch_bytes, void* gate,
-                       int gate_n, void* stream) {
+                       int gate_n, void* stream, gm_lr_state* lrs = nullptr) {
     // (main, bypass) groups per branch: 4 for the two-branch gate, 2 nb for the N-branch one (nb in
     // the state: the rule reads 4 nb sums)
     GM_REQUIRE(!gate || (gate_n ? (ngroups >= 4 && ngroups % 2 == 0) : ngroups == 4),
@@ -366,7 +410,11 @@ static int group_sumsq(const gm_tensor* table, float* const* mom, int nt, long l
     double* rows = (double*)scratch;
     const bool few = ngroups <= 8;  // else the N-branch gates (C5: 12 branches -> 24 groups)
     const bool plain = form == upd::none || form == upd::sgd;
-    if (plain) {
+    if (lrs) {
+        const auto k = form == upd::sgd ? dlr_kernel<upd::sgd>(few)
+                                        : (form == upd::mom ? dlr_kernel<upd::mom>(few) : dlr_kernel<upd::decay>(few));
+        k<<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h.gscale, lrs, h.mu, h.wd, chunk, rows);
+    } else if (plain) {
         const bool sgd = form == upd::sgd;
         const auto k = few ? (sgd ? k_group_sumsq<true, 8> : k_group_sumsq<false, 8>)
                            : (sgd ? k_group_sumsq_runs<true> : k_group_sumsq_runs<false>);
@@ -377,9 +425,10 @@ static int group_sumsq(const gm_tensor* table, float* const* mom, int nt, long l
                            : (mo ? k_group_sumsq_sgdm_runs<true> : k_group_sumsq_sgdm_runs<false>);
         k<<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h, chunk, rows);
     }
-    int rc = check_launch(plain ? "k_group_sumsq" : "k_group_sumsq_sgdm");
+    int rc = check_launch(lrs ? "k_group_sumsq_dlr" : (plain ? "k_group_sumsq" : "k_group_sumsq_sgdm"));
     if (rc) return rc;
-    k_group_finalize<<<1, kFinT, 0, st>>>(rows, nb, ngroups, out, gate, gate && gate_n ? 1 : 0);
+    if (lrs) k_group_finalize_lr<<<1, kFinT, 0, st>>>(rows, nb, ngroups, out, gate, gate && gate_n ? 1 : 0, lrs);
+    else k_group_finalize<<<1, kFinT, 0, st>>>(rows, nb, ngroups, out, gate, gate && gate_n ? 1 : 0);
     return check_launch("k_group_finalize");
 }
 
@@ -408,4 +457,35 @@ extern "C" int gm_group_sumsq_sgdm(const gm_tensor* table, float* const* mom, in
                "group_sumsq_sgdm: momentum buffers must be given if and only if momentum != 0");
     return group_sumsq(table, mom, nt, total, ngroups, {gscale, lr, momentum, weight_decay},
                        mom ? upd::mom : upd::decay, out, scratch, scratch_bytes, gate, gate_n, stream);
+}
+
+extern "C" int gm_group_sumsq_lr(const gm_tensor* table, float* const* mom, int nt, long long total, int ngroups,
+                                 float gscale, gm_lr_state* lr, float momentum, float weight_decay, double* out,
+                                 void* scratch, size_t scratch_bytes, void* gate, int gate_n, void* stream) {
+    GM_REQUIRE(lr, "group_sumsq_lr: null lr state");
+    GM_REQUIRE(std::isfinite(momentum) && momentum >= 0.f, "group_sumsq_lr: momentum must be finite and >= 0");
+    GM_REQUIRE(std::isfinite(weight_decay) && weight_decay >= 0.f,
+               "group_sumsq_lr: weight_decay must be finite and >= 0");
+    GM_REQUIRE((mom != nullptr) == (momentum != 0.f),
+               "group_sumsq_lr: momentum buffers must be given if and only if momentum != 0");
+    const upd form = mom ? upd::mom : (weight_decay != 0.f ? upd::decay : upd::sgd);
+    return group_sumsq(table, mom, nt, total, ngroups, {gscale, 0.f, momentum, weight_decay}, form, out, scratch,
+                       scratch_bytes, gate, gate_n, stream, lr);
+}
+
+extern "C" int gm_lr_at(const gm_lr_state* s, long long t, float* lr_out) {
+    GM_REQUIRE(s && lr_out, "lr_at: null argument");
+    GM_REQUIRE(t >= 0, "lr_at: pass index must be >= 0");
+    GM_REQUIRE(s->kind == kLrHeld || s->kind == kLrMultistep || s->kind == kLrCosine, "lr_at: unknown kind %d",
+               s->kind);
+    const auto rate = [](double v) { return std::isfinite(v) && v >= 0.0; };
+    GM_REQUIRE(rate(s->lr) && rate(s->base_lr) && rate(s->min_lr), "lr_at: rates must be finite and >= 0");
+    GM_REQUIRE(rate(s->gamma) && rate(s->warmup_start), "lr_at: gamma and warmup_start must be finite and >= 0");
+    GM_REQUIRE(s->warmup_steps >= 0, "lr_at: warmup_steps must be >= 0");
+    GM_REQUIRE(s->n_milestones >= 0 && s->n_milestones <= GM_LR_MAX_MILESTONES, "lr_at: n_milestones must be 0..%d",
+               GM_LR_MAX_MILESTONES);
+    GM_REQUIRE(s->kind != kLrCosine || s->total_steps > s->warmup_steps,
+               "lr_at: cosine needs total_steps > warmup_steps");
+    *lr_out = lr_rule(*s, t);
+    return 0;
 }

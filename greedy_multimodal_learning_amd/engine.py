@@ -263,10 +263,17 @@ class BalancedStep:
     def __init__(self, model, lr=0.1, gate=None, compute_dtype=torch.bfloat16, channels_last=True,
                  process_group=None, bucket_mb=25.0, branchnames=("net_view_0", "net_view_1"),
                  MMTMnames=("visual", "skeleton"), graphs=False, device_gate=None, dp_buckets=None,
-                 mmtm_excite=None, f32_contraction=None, momentum=0.0, weight_decay=0.0):
+                 mmtm_excite=None, f32_contraction=None, momentum=0.0, weight_decay=0.0, lr_schedule=None):
         import math
         self.model = model
-        self.lr = float(lr)
+        # lr_schedule (an lr_schedule.LRSchedule; None: the rate is the `lr` argument of the update
+        # kernels and part of every captured graph's key): the rate lives in a device gm_lr_state
+        # (self.lr_state, made below, before any capture), the update kernels read it there and the
+        # finalize launch advances it, so one captured graph serves every rate
+        self.lr_schedule = lr_schedule
+        self.lr_state = None
+        self._lr_t = 0  # update passes applied under the schedule (host mirror of gm_lr_state.step)
+        self._lr = float(lr) if lr_schedule is None else lr_schedule.base_lr  # (a schedule's base_lr replaces lr)
         # torch.optim.SGD's momentum and weight decay (dampening 0, no Nesterov term), fixed per
         # engine; both 0 (the default): the plain update, no momentum buffer
         self.momentum, self.weight_decay = float(momentum), float(weight_decay)
@@ -304,6 +311,8 @@ class BalancedStep:
             from . import vtrunk
             vtrunk._wgrad_stream(self.device)  # (the stacked trunk's weight-gradient stream, likewise)
         self.norms = GroupNorms(named, list(branchnames), list(MMTMnames))
+        if lr_schedule is not None:
+            self.lr_state = torch.frombuffer(bytearray(lr_schedule.pack(0)), dtype=torch.uint8).to(self.device)
         # one flat zero momentum buffer at FlatParams' offsets (so co-aligned with the parameter
         # and gradient buffers: the fused pass keeps its 16-byte path), made here, before any
         # capture: the graph mutates it in place
@@ -459,7 +468,57 @@ class BalancedStep:
             kw = dict(momentum=self.momentum, weight_decay=self.weight_decay, momentum_buffers=self._mom_bufs)
         if self.device_gate:
             kw.update(gate=self.gate_state, gate_n=self.gate_n)
+        if self.lr_state is not None:  # gm_group_sumsq_lr: the rate is read from (and advanced in) device memory
+            return self.norms.sums(grad_scale=1.0 / self.world, lr_state=self.lr_state, **kw)
         return self.norms.sums(grad_scale=1.0 / self.world, lr=self.lr, **kw)
+
+    # ---------------- learning rate ----------------
+    @property
+    def lr(self):
+        """The rate the next step's update uses.  Under a device-run schedule: lr_at(passes so
+        far), from the host mirror of the pass count (no sync)."""
+        sch = self.lr_schedule
+        if sch is not None and sch.device_run:
+            return sch.lr_at(self._lr_t)
+        return self._lr
+
+    @lr.setter
+    def lr(self, value):
+        value = float(value)
+        sch = self.lr_schedule
+        if sch is None:
+            self._lr = value
+            return
+        if sch.device_run:
+            raise ValueError(f"BalancedStep.lr: the {sch.kind} schedule owns the rate on the device "
+                             "(set_lr_step moves it)")
+        if value != self._lr:  # held: a stream-ordered fill of the state's first four bytes, no re-capture
+            self.lr_state[:4].view(torch.float32).fill_(value)
+            self._lr = value
+
+    def _lr_key(self):
+        """The rate's part of a graph key: the rate itself when the kernels take it as an
+        argument, a constant when they read it from the device state"""
+        return self._lr if self.lr_state is None else "device-lr"
+
+    def sync_lr(self):
+        """The device gm_lr_state as its ctypes mirror (LrState: lr, step, ...); one host sync,
+        for tests and checkpoints.  None without a schedule."""
+        if self.lr_state is None:
+            return None
+        from .lr_schedule import unpack
+        return unpack(self.lr_state.cpu().numpy().tobytes())
+
+    def set_lr_step(self, t):
+        """A resumed run: the state of a run that has applied t update passes (step = t, lr =
+        lr_at(t); held keeps its rate), written on the current stream."""
+        if self.lr_state is None:
+            raise ValueError("BalancedStep.set_lr_step: no lr_schedule")
+        st = self.lr_schedule.struct(int(t))
+        if not self.lr_schedule.device_run:
+            st.lr = self._lr
+        self.lr_state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8))
+        self._lr_t = int(t)
 
     def momentum_buffer(self, p):
         """The momentum buffer of parameter p: a view of the flat buffer shaped and strided like
@@ -566,9 +625,9 @@ class BalancedStep:
 
     def _graph_key(self):
         if self.device_gate:
-            return ("device-gate", self.lr)
+            return ("device-gate", self._lr_key())
         fl = self.flags
-        return (bool(fl.curation_mode), fl.caring_modality if fl.curation_mode else None, self.lr)
+        return (bool(fl.curation_mode), fl.caring_modality if fl.curation_mode else None, self._lr_key())
 
     def bind_batches(self, *pairs):
         """Register device batches (x, y) as static graph inputs.  A step on a bound
@@ -650,7 +709,7 @@ class BalancedStep:
             if entry is None:
                 # a learning-rate change (ReduceLROnPlateau) makes the old-lr graphs dead weight;
                 # the last replay may still be running: destroy nothing before it is done
-                stale = [k for k in self._graphs if k[0][-1] != self.lr]
+                stale = [k for k in self._graphs if k[0][-1] != self._lr_key()]
                 if stale:
                     torch.cuda.synchronize(self.device)
                 for k in stale:
@@ -735,6 +794,8 @@ class BalancedStep:
             gate.pending_sums = None
         self.last_loss = loss
         self.step_count += 1
+        if self.lr_state is not None:
+            self._lr_t += 1
         return loss
 
     def on_epoch_begin(self, epoch):

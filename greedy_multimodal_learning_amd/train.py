@@ -183,7 +183,8 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
                   valid=None, test=None, test_steps=None, validation_steps=None, use_gpu=True, device_numbers=[0],
                   custom_callbacks=[], checkpoint_monitor="val_acc", n_epochs=100, verbose=True, nummodalities=2,
                   compute_dtype="fp32", graphs=True, f32_contraction="exact", eval_engine="modules",
-                  eval_f32_trunk="modules", fused_momentum=False):
+                  eval_f32_trunk="modules", fused_momentum=False, lr_schedule=None, lr_warmup_steps=0,
+                  lr_warmup_start=0.0, lr_milestones=(), lr_gamma=0.1, lr_total_steps=None, lr_min=0.0):
     """Reference src/training_loop.py:86-143 + Model_.train_loop (src/framework.py:
     250-330) on the fused engine.  `optimizer` is the (lr, momentum, wd) triple of the
     reference's SGD (a torch SGD over the model's parameters holds the learning rate and
@@ -202,7 +203,17 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
     epoch) hold {'model', 'optimizer'} (src/training_loop.py:26-48, src/utils.py:107-115).
     `eval_engine`: "modules" (the default: the module forward in eval mode) or "fused" (an
     engine.EvalStep runs the validation / test passes).  `eval_f32_trunk`: "modules" (the
-    default) or "fused" (fp32 with eval_engine "fused" only: the fp32 eval trunk, eval_engine_arg)."""
+    default) or "fused" (fp32 with eval_engine "fused" only: the fp32 eval trunk, eval_engine_arg).
+    `lr_schedule` (None, the default: the rate is a kernel argument and a change of it a new
+    captured graph; or "held", "multistep", "cosine"): the rate lives on the device and one
+    captured step serves every rate (lr_schedule.LRSchedule with base_lr = the optimizer's lr and
+    `lr_warmup_steps`, `lr_warmup_start`, `lr_milestones`, `lr_gamma`, `lr_total_steps`, `lr_min`;
+    all counts in optimizer steps, `lr_total_steps=None`: (n_epochs - 1) * steps_per_epoch).
+    "held" leaves the rate to the host (ReduceLROnPlateau_PyTorch keeps working, without a
+    re-capture); "multistep" and "cosine" run on the device and refuse ReduceLROnPlateau_PyTorch
+    (two owners of one rate).  With a schedule each epoch's logs get `lr` (the rate after the
+    epoch's last step), the checkpoint's optimizer carries that rate and the checkpoint an
+    `lr_schedule` entry {params, step}."""
     import math
 
     from .engine import BalancedStep
@@ -211,6 +222,19 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
         raise NotImplementedError("by default the fused step implements SGD with momentum = weight_decay = 0 "
                                   "(train.momentum / train.wd of every reference config); bind "
                                   "training_loop.fused_momentum=True for the fused momentum / weight-decay update")
+    sched = None
+    if lr_schedule is not None:
+        from .lr_schedule import LRSchedule
+        total = lr_total_steps
+        if total is None and lr_schedule == "cosine" and steps_per_epoch is not None:
+            total = (n_epochs - 1) * steps_per_epoch
+        sched = LRSchedule(lr_schedule, lr, warmup_steps=lr_warmup_steps, warmup_start=lr_warmup_start,
+                           milestones=lr_milestones, gamma=lr_gamma, total_steps=total, min_lr=lr_min)
+        if sched.device_run and any(isinstance(c, avail_callbacks.ReduceLROnPlateau_PyTorch)
+                                    for c in custom_callbacks):
+            raise ValueError(f"training_loop.lr_schedule={lr_schedule!r} runs the rate on the device and "
+                             "ReduceLROnPlateau_PyTorch drives it from the host: one rate, two owners "
+                             "(use lr_schedule='held' with ReduceLROnPlateau_PyTorch)")
     dev = torch.device("cuda", device_numbers[0])
     model = model.to(dev)
     gates = [c for c in custom_callbacks if hasattr(c, "on_backward_end")
@@ -221,7 +245,7 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
     cdt = _DTYPES[compute_dtype]
     step = BalancedStep(model, lr=lr, gate=gate, compute_dtype=cdt, channels_last=True, graphs=graphs,
                         f32_contraction=f32_contraction_arg(cdt, f32_contraction), momentum=momentum,
-                        weight_decay=wd)
+                        weight_decay=wd, lr_schedule=sched)
     # the reference's optimizer object (never stepped: the engine's fused pass applies the
     # update with the learning rate read from it)
     opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=wd)
@@ -259,7 +283,8 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
                 break
             for c in others:
                 c.on_batch_begin(bi + 1, {})
-            step.lr = float(opt.param_groups[0]["lr"])
+            if sched is None or not sched.device_run:  # (held: a 4-byte fill when the rate changed)
+                step.lr = float(opt.param_groups[0]["lr"])
             loss = step(x, y)
             outs = step.last_outs
             with torch.no_grad():  # Model_._compute_loss_and_metrics (src/framework.py:152-156)
@@ -298,6 +323,8 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
                 "train_indices": np.concatenate(idxs) if idxs else np.zeros(0, np.int64)}
         if gate is not None:
             logs.update({"d_BDR": d_bdr, "curation_mode": cur, "caring_modality": caring})
+        if sched is not None:
+            logs["lr"] = step.lr
         # validation / test with the model's current curation flags (src/framework.py:146-148)
         if step.device_gate:
             step.sync_gate()
@@ -318,7 +345,11 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
             if step.flat_momentum is not None:  # what the reference's stepped SGD would hold
                 for p in model.parameters():
                     opt.state[p]["momentum_buffer"] = step.momentum_buffer(p).detach().clone()
+            if sched is not None and sched.device_run:
+                opt.param_groups[0]["lr"] = step.lr
             ck = {"model": model.state_dict(), "optimizer": opt.state_dict()}
+            if sched is not None:
+                ck["lr_schedule"] = {"params": sched.params(), "step": int(step.sync_lr().step)}
             mon = logs.get(checkpoint_monitor)
             if mon is not None and (best is None or mon > best):
                 best = mon

@@ -385,6 +385,48 @@ int gm_group_sumsq_sgdm(const gm_tensor* table, float* const* mom, int ntensors,
                         void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Device-resident learning rate: the rate the update reads lives in a small caller-owned DEVICE
+ * struct and its schedule advances in the pass's finalize launch, so a captured step (hipGraph)
+ * serves every rate - warm-up and per-step decay without a re-capture or a host sync.
+ * With t the 0-based index of the update pass, W = warmup_steps, s = warmup_start, T = total_steps,
+ * in fp64 with one rounding to fp32:
+ *     w(t) = (W > 0 && t < W) ? s + (1 - s) * (t / W) : 1
+ *   held      (kind 0): lr is whatever the host last wrote; only `step` advances
+ *   multistep (kind 1): lr = (base_lr * w(t)) * gamma^(number of i < n_milestones with
+ *                       t >= milestones[i]); a milestone listed twice counts twice
+ *                       (torch.optim.lr_scheduler.MultiStepLR)
+ *   cosine    (kind 2): t < W: lr = base_lr * w(t); else with tt = min(t, T)
+ *                       lr = min_lr + (base_lr - min_lr) * 0.5 * (1 + cos(pi * (tt - W) / (T - W)))
+ * C callers name the type by its tag, `struct gm_lr_state`.
+ * ------------------------------------------------------------------------- */
+#define GM_LR_MAX_MILESTONES 8
+struct gm_lr_state {
+    float lr;                 /* offset 0: the rate the NEXT update pass reads */
+    int kind;                 /* 0 held (host-set), 1 multistep, 2 cosine */
+    long long step;           /* update passes applied so far */
+    double base_lr, min_lr, gamma, warmup_start;
+    long long warmup_steps, total_steps;
+    int n_milestones, pad_;
+    long long milestones[GM_LR_MAX_MILESTONES];
+};
+/* gm_group_sumsq_sgdm with the rate read from *lr (DEVICE, read once per workgroup) instead of an
+ * argument.  The update always runs (a rate of 0 included): momentum == 0 && weight_decay == 0
+ * without buffers is gm_group_sumsq's update, weight_decay alone keeps b' = d in registers,
+ * buffers give the momentum form; the argument rules are gm_group_sumsq_sgdm's.  Sums, parameters
+ * and buffers are bit-identical to the scalar entry points' at the same rate.  After the sums
+ * (and the gate's rule) the finalize launch advances the state: step += 1 and, unless held,
+ * lr = rule(step), so the next pass in stream (or graph) order reads the next rate. */
+int gm_group_sumsq_lr(const gm_tensor* table, float* const* mom, int ntensors, long long total,
+                      int ngroups, float grad_scale, struct gm_lr_state* lr, float momentum,
+                      float weight_decay, double* out, void* scratch, size_t scratch_bytes,
+                      void* gate, int gate_n, void* stream);
+/* Host only: the rate pass t reads, by the rule above, from a HOST copy of the state; refuses
+ * what a device state cannot be checked for (unknown kind, cosine with total_steps <=
+ * warmup_steps, n_milestones outside 0..GM_LR_MAX_MILESTONES, a negative or non-finite rate,
+ * gamma or warmup_start, negative counts). */
+int gm_lr_at(const struct gm_lr_state* host_state, long long t, float* lr_out);
+
+/* ---------------------------------------------------------------------------
  * ResNet trunk convolutions (torchvision resnet18/50 Conv2d, bias=False; called
  * piecewise at reference src/model.py:65-106) as bf16 implicit GEMMs on MFMA.
  * Activations NHWC [N][H][W][C] bf16, weights KRSC [K][R][S][C] bf16 (PyTorch

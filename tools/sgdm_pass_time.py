@@ -1,12 +1,19 @@
 """Time the norms+update pass in its three forms at the C2 parameter set (MMTM_MVCNN, 2 views:
 23,773,008 elements in the engine's flat buffers): the plain update (gm_group_sumsq, 12 B per
 element), weight decay alone (gm_group_sumsq_sgdm without buffers, 12 B) and momentum + weight
-decay (20 B).  One process, the forms interleaved launch by launch within a round, HIP events
-around each launch pair (pass + finalize) behind a device sleep, as bench.time_group_sumsq does;
-prints one JSON line: per form the median over rounds of the round's mean, the spread over the
-rounds, and the achieved bytes/s against the 8.0 TB/s HBM3E peak.
+decay (20 B), each next to its device-rate sibling (`*_dlr`: gm_group_sumsq_lr, the rate read
+from a held gm_lr_state holding the same value; `dlr_minus_scalar_us`: the pair's difference of
+medians, to be read against the larger of the pair's spreads).  One process, the forms
+interleaved launch by launch within a round, HIP events around each launch pair (pass +
+finalize) behind a device sleep, as bench.time_group_sumsq does; prints one JSON line: per form
+the median over rounds of the round's mean, the spread over the rounds, and the achieved bytes/s
+against the 8.0 TB/s HBM3E peak.
 
-    python tools/sgdm_pass_time.py [--rounds 7] [--launches 20] [--out FILE]
+    python tools/sgdm_pass_time.py [--rounds 7] [--launches 20] [--swap] [--out FILE]
+
+A launch's time depends on what the launch before it left in the caches (the momentum forms touch
+a third 95 MB buffer).  --swap runs each pair device-rate first on every other launch, so both
+members of a pair follow the same predecessors equally often.
 """
 import argparse
 import json
@@ -23,6 +30,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--swap", action="store_true", help="alternate the order within each scalar / device-rate pair")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -40,32 +48,43 @@ def main():
         "weight_decay": (12, dict(weight_decay=5e-4)),
         "momentum": (20, dict(momentum=0.9, weight_decay=5e-4, momentum_buffers=st._mom_bufs)),
     }
+    from greedy_multimodal_learning_amd.lr_schedule import LRSchedule
+    state = torch.frombuffer(bytearray(LRSchedule("held", st.lr).pack()), dtype=torch.uint8).to(dev)
+    scalar = list(forms)
+    forms = {k + suffix: (bpe, dict(kw, **extra)) for k, (bpe, kw) in forms.items()
+             for suffix, extra in (("", dict(lr=st.lr)), ("_dlr", dict(lr_state=state)))}
     stream = torch.cuda.current_stream()
     for _, kw in forms.values():  # warm up every form
         for _ in range(3):
-            st.norms.sums(lr=st.lr, **kw)
+            st.norms.sums(**kw)
     means = {k: [] for k in forms}
     for _ in range(a.rounds):
         torch.cuda.synchronize()
         torch.cuda._sleep(50_000_000)
         evs = {k: [] for k in forms}
-        for _ in range(a.launches):
-            for k, (_, kw) in forms.items():
+        for li in range(a.launches):
+            order = list(forms)
+            if a.swap and li % 2:
+                order = [k for i in range(0, len(order), 2) for k in (order[i + 1], order[i])]
+            for k in order:
+                kw = forms[k][1]
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
-                st.norms.sums(lr=st.lr, **kw)
+                st.norms.sums(**kw)
                 e1.record(stream)
                 evs[k].append((e0, e1))
         torch.cuda.synchronize()
         for k in forms:
             means[k].append(sum(x.elapsed_time(y) for x, y in evs[k]) / a.launches * 1e3)  # us
-    res = {"elements": n, "rounds": a.rounds, "launches_per_round": a.launches}
+    res = {"elements": n, "rounds": a.rounds, "launches_per_round": a.launches, "swap": a.swap}
     for k, (bpe, _) in forms.items():
         med = statistics.median(means[k])
         res[k] = {"us": round(med, 2), "spread_us": round(max(means[k]) - min(means[k]), 2),
                   "bytes": bpe * n, "tb_per_s": round(bpe * n / (med * 1e-6) / 1e12, 3),
                   "hbm_peak_fraction": round(bpe * n / (med * 1e-6) / HBM_PEAK, 3)}
     res["momentum_over_plain"] = round(res["momentum"]["us"] / res["plain"]["us"], 3)
+    for k in scalar:
+        res[k + "_dlr"]["dlr_minus_scalar_us"] = round(res[k + "_dlr"]["us"] - res[k]["us"], 2)
     assert torch.isfinite(st.flat.param).all() and torch.isfinite(st.flat_momentum).all()
     line = json.dumps(res)
     print(line)
