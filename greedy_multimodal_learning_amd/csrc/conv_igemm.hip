@@ -27,12 +27,6 @@
 
 static void pack_grid(ConvCls& c, int S);
 
-static int ilog2(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return (1 << l) == v ? l : -1;
-}
-
 // the class's taps as a grid: rows r (stride-compatible with the class parity ph) and
 // columns s (with pw); fwd is the st = 1 case with every (r, s) - same order as tw/dh/dw
 static void set_grid(ConvCls& c, const gm_conv_desc* d, int st, int ph, int pw) {
@@ -110,7 +104,7 @@ static int check_desc(const gm_conv_desc* d) {
                "conv: empty shape");
     GM_REQUIRE(d->stride >= 1 && d->pad >= 0, "conv: bad stride/pad");
     GM_REQUIRE(d->R * d->S <= kMaxTap, "conv: at most %d taps", kMaxTap);
-    GM_REQUIRE(ilog2(d->C) >= 3, "conv: C must be a power of two >= 8 (got %d)", d->C);
+    GM_REQUIRE(log2_exact(d->C) >= 3, "conv: C must be a power of two >= 8 (got %d)", d->C);
     GM_REQUIRE(d->K % 8 == 0, "conv: K must be a multiple of 8 (got %d)", d->K);
     return GM_OK;
 }
@@ -120,7 +114,7 @@ static int check_desc_hw(const gm_conv_desc_hw* d) {
                "conv: empty shape");
     GM_REQUIRE(d->stride_h >= 1 && d->stride_w >= 1 && d->pad_h >= 0 && d->pad_w >= 0, "conv: bad stride/pad");
     GM_REQUIRE(d->R * d->S <= kMaxTap, "conv: at most %d taps", kMaxTap);
-    GM_REQUIRE(ilog2(d->C) >= 3, "conv: C must be a power of two >= 8 (got %d)", d->C);
+    GM_REQUIRE(log2_exact(d->C) >= 3, "conv: C must be a power of two >= 8 (got %d)", d->C);
     GM_REQUIRE(d->K % 8 == 0, "conv: K must be a multiple of 8 (got %d)", d->K);
     GM_REQUIRE(d->H + 2 * d->pad_h >= d->R && d->W + 2 * d->pad_w >= d->S, "conv: filter larger than input");
     return GM_OK;
@@ -132,7 +126,7 @@ static void fwd_setup(const gm_conv_desc_hw* d, const void* x, const void* w, vo
     memset(&a, 0, sizeof(a));
     a.in = (const uint16_t*)x;
     a.wt = (const uint16_t*)w;
-    a.N = d->N; a.Hi = d->H; a.Wi = d->W; a.C = d->C; a.logC = ilog2(d->C);
+    a.N = d->N; a.Hi = d->H; a.Wi = d->W; a.C = d->C; a.logC = log2_exact(d->C);
     a.Nout = d->K; a.T = d->R * d->S; a.Sw = d->S;
     a.Ho = P; a.Wo = Q; a.sAh = d->stride_h; a.sAw = d->stride_w;
     a.ncls = 1;
@@ -159,7 +153,7 @@ static bool dgrad_setup(const gm_conv_desc* d, const void* dy, const void* wt, v
     memset(&a, 0, sizeof(a));
     a.in = (const uint16_t*)dy;
     a.wt = (const uint16_t*)wt;
-    a.N = d->N; a.Hi = P; a.Wi = Q; a.C = d->K; a.logC = ilog2(d->K);
+    a.N = d->N; a.Hi = P; a.Wi = Q; a.C = d->K; a.logC = log2_exact(d->K);
     a.Nout = d->C; a.T = d->R * d->S; a.Sw = d->S;
     a.Ho = d->H; a.Wo = d->W; a.sAh = a.sAw = 1;
     a.G = 1;
@@ -193,7 +187,7 @@ static bool dgrad_setup(const gm_conv_desc* d, const void* dy, const void* wt, v
 static int check_dgrad(const gm_conv_desc* d) {
     int rc = check_desc(d);
     if (rc) return rc;
-    GM_REQUIRE(ilog2(d->K) >= 3, "conv dgrad: K must be a power of two >= 8 (got %d)", d->K);
+    GM_REQUIRE(log2_exact(d->K) >= 3, "conv dgrad: K must be a power of two >= 8 (got %d)", d->K);
     GM_REQUIRE(d->stride * d->stride <= kMaxCls, "conv dgrad: stride %d unsupported", d->stride);
     return GM_OK;
 }

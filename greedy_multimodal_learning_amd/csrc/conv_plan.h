@@ -88,17 +88,6 @@ static bool lean_ok(const ConvArgs& a) {
     return grid;
 }
 
-static int conv_cus() {
-    static int n = [] {
-        int dev = 0, c = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0)
-            c = 256;
-        return c;
-    }();
-    return n;
-}
-
 static long conv_pixels(const ConvArgs& a) {
     long M = 0;
     for (int i = 0; i < a.ncls; ++i) M += (long)a.N * a.cls[i].P * a.cls[i].Q * a.G;
@@ -436,16 +425,7 @@ static ConvPlan plan_conv(const ConvArgs& a, size_t ws_bytes, const ConvKnobs& k
 // one kernel instantiation: grow its dynamic LDS limit when this launch needs more, launch
 template <auto Kern, class... Extra>
 static int launch_form(const char* name, ConvArgs& a, const ConvPlan& p, hipStream_t st, const Extra&... extra) {
-    static size_t granted = 0;  // largest dynamic LDS granted so far (idempotent, safe to race)
-    if (p.lds > granted) {
-        const hipError_t e =
-            hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-        if (e != hipSuccess) {
-            set_error("%s: %zu B of LDS refused (%s)", name, p.lds, hipGetErrorString(e));
-            return GM_E_UNSUP;
-        }
-        granted = p.lds;
-    }
+    if (int rc = grant_lds<Kern>(name, p.lds)) return rc;
     Kern<<<p.grid, p.wg, p.lds, st>>>(a, extra...);
     return check_launch(name);
 }

@@ -113,6 +113,40 @@ struct FastDiv {
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// log2 of a power of two, -1 for anything else
+inline int log2_exact(int v) {
+    int l = 0;
+    while ((1 << l) < v) ++l;
+    return (1 << l) == v ? l : -1;
+}
+
+// the CU count the convolution planners (conv_plan.h, conv_wgrad_plan.h) size their grids by:
+// the current device's, or the MI355X's 256 where no device answers (size queries on a CPU box)
+inline int conv_cus() {
+    static const int n = [] {
+        int dev = 0, c = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0)
+            c = 256;
+        return c;
+    }();
+    return n;
+}
+
+// one kernel instantiation's dynamic LDS limit, grown when a launch needs more than was granted
+template <auto Kern>
+int grant_lds(const char* name, size_t bytes) {
+    static size_t granted = 0;  // largest dynamic LDS granted so far (idempotent, safe to race)
+    if (bytes <= granted) return GM_OK;
+    const hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) {
+        set_error("%s: %zu B of LDS refused (%s)", name, bytes, hipGetErrorString(e));
+        return GM_E_UNSUP;
+    }
+    granted = bytes;
+    return GM_OK;
+}
+
 // ---- in-launch hand-off health (fused BatchNorm, split-K turnstile) ----------------
 // A spin that runs out of its poll budget sets a bit in its translation unit's sticky
 // device fault word and poisons its result (NaN) instead of applying stale data;

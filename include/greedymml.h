@@ -473,7 +473,7 @@ int gm_conv_set_h9(int on);
 /* Split-K target: workgroups wanted from splitting K of 128x128-tile convolutions whose
  * tiles alone do not fill the device (default 384; 0 = never). */
 int gm_conv_set_splitk(int target);
-/* Weight-gradient kernel choice (default 22): bit 1 = k_wgrad_halo64 (64 x 9 x 64
+/* Weight-gradient kernel choice (default 22 = bits 1, 2 and 4): bit 1 = k_wgrad_halo64 (64 x 9 x 64
  * gradient blocks in one workgroup's accumulators, one input row staged per output row, dedicated
  * loader waves) for 3x3 / s1 shapes with 64 channels, bit 2 = also for 128 channels, bit 3 = up to
  * 512; bit 4 = k_wgrad_ring for the other 3x3 shapes with K % 128 == 0 and C a power of two >= 32

@@ -12,7 +12,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-WGRAD_LOOP_DEFAULT = 22  # gm_conv_set_wgrad_loop's default (conv_wgrad.hip g_wgrad_loop)
+WGRAD_LOOP_DEFAULT = 22  # gm_conv_set_wgrad_loop's default (conv_wgrad_plan.h WgradKnobs::loop)
 
 SHAPES = [  # N, C, H, W, K, R, S, stride, pad
     (2, 64, 56, 56, 64, 3, 3, 1, 1),

@@ -42,7 +42,7 @@ pytestmark = pytest.mark.gpu
 
 CL = torch.channels_last
 BF = torch.bfloat16
-WGRAD_LOOP_DEFAULT = 22   # gm_conv_set_wgrad_loop's default (conv_wgrad.hip g_wgrad_loop)
+WGRAD_LOOP_DEFAULT = 22   # gm_conv_set_wgrad_loop's default (conv_wgrad_plan.h WgradKnobs::loop)
 _ids = lambda s: "x".join(map(str, s))  # noqa: E731
 
 
@@ -442,7 +442,7 @@ def test_affine_epilogue_rounds_once(dev, shape, mags, other):
 
 # ---- 5. weight gradients: fp32 out, torch.equal to the exact reference -----------------------------
 # (N, C, H, W, K, R, stride, pad), knobs: the kernel they force (as the neighbouring tests do)
-# Slabs: k_conv_wgrad4's plan (conv_wgrad.hip plan()) splits the 64-pixel steps over workgroups only from 16
+# Slabs: k_conv_wgrad4's plan (conv_wgrad_plan.h plan_wgrad4()) splits the 64-pixel steps over workgroups only from 16
 # steps (>= 8 per split); "direct" rows write the gradient from one workgroup per tile, "split" rows through
 # partial slabs and the fixed-order sum.  gm_conv_set_wgrad_staging picks the kernel's operand staging (its WR
 # template argument): 1 registers, 0 LDS-DMA; the default (2) takes registers for 1x1 filters only.
@@ -466,14 +466,24 @@ WGRAD_ROWS = [(s, dict(wgrad_loop=0, wgrad_staging=wr), f"k_conv_wgrad4 {what}, 
     ((3, 256, 14, 14, 256, 3, 1, 1), dict(wgrad_loop=16), "k_wgrad_ring"),
     ((5, 128, 9, 11, 128, 3, 2, 1), dict(wgrad_loop=16), "k_wgrad_ring strided, ragged M"),
     ((2, 32, 7, 5, 128, 3, 1, 1), dict(wgrad_loop=16), "k_wgrad_ring, C = 32"),
+    # a cropped gradient (c_real < C, a fourth element) under the default knobs: the shape's dedicated kernel
+    # must not take it - k_conv_wgrad4 without its direct form, then k_wgrad_reduce
+    ((2, 64, 9, 7, 64, 3, 1, 1), {}, "halo64-eligible, c_real 61: k_conv_wgrad4, 1 slab, k_wgrad_reduce", 61),
+    ((5, 256, 14, 14, 256, 3, 1, 1), {}, "ring-eligible, c_real 250: k_conv_wgrad4, 2 slabs, k_wgrad_reduce", 250),
 ]
 
 
-@pytest.mark.parametrize("shape,kn,path", WGRAD_ROWS,
-                         ids=[f"{_ids(r[0])}-{'_'.join(f'{k}{v}' for k, v in r[1].items())}" for r in WGRAD_ROWS])
-def test_wgrad_bit_exact(dev, shape, kn, path):
+def _wgrad_id(r):
+    return f"{_ids(r[0])}-{'_'.join(f'{k}{v}' for k, v in r[1].items())}" + (f"c_real{r[3]}" if len(r) > 3 else "")
+
+
+@pytest.mark.parametrize("shape,kn,path,c_real", [r if len(r) > 3 else r + (r[0][1],) for r in WGRAD_ROWS],
+                         ids=[_wgrad_id(r) for r in WGRAD_ROWS])
+def test_wgrad_bit_exact(dev, shape, kn, path, c_real):
     """gm_conv2d_wgrad_grouped_bf16 over two view groups, plain and accumulating onto an integer base:
-    the fp32 gradient == the exact one (a bf16 partial, a lost or doubled slab changes an integer)."""
+    the fp32 gradient == the exact one (a bf16 partial, a lost or doubled slab changes an integer).
+    c_real < C: the gradient of the first c_real input channels, groups K*R*R*c_real floats apart, with
+    every channel of x non-zero (a wrong crop changes an integer) and nothing written past the last group."""
     from greedy_multimodal_learning_amd import _lib as L
     from greedy_multimodal_learning_amd import conv as CV
     lib = L.load()
@@ -486,6 +496,8 @@ def test_wgrad_bit_exact(dev, shape, kn, path):
     g = torch.Generator().manual_seed(sum(shape))
     x = E.ints((G * N, H, W, C), mx, g)
     dy = E.ints((G * N, P, Q, K), md, g)
+    if c_real < C:
+        x[x == 0] = mx
     refs = []
     for gi in range(G):
         xr, gr = x[gi * N:(gi + 1) * N].permute(0, 3, 1, 2), dy[gi * N:(gi + 1) * N].permute(0, 3, 1, 2)
@@ -494,7 +506,7 @@ def test_wgrad_bit_exact(dev, shape, kn, path):
             assert torch.equal(torch.nn.grad.conv2d_weight(xr.double(), (K, C, R, R), gr.double(), stride=st,
                                                            padding=pad), ref.double())
         assert float(ref.abs().max()) > 8
-        refs.append(ref.permute(0, 2, 3, 1))   # KRSC
+        refs.append(ref.permute(0, 2, 3, 1)[..., :c_real])   # KRSC, the first c_real input channels
     xd, dyd = x.to(BF).to(dev), dy.to(BF).to(dev)
     d = CV._desc_hw(N, H, W, C, K, R, R, st, st, pad, pad)
     outs = []
@@ -502,11 +514,13 @@ def test_wgrad_bit_exact(dev, shape, kn, path):
         need = lib.gm_conv2d_wgrad_grouped_scratch(ctypes.byref(d), G)
         scr = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
         for acc in (0, 1):
-            dw = torch.full((G, K, R, R, C), base, device=dev, dtype=torch.float32)
+            n = K * R * R * c_real
+            dw = torch.full((G * n + 64,), base, device=dev, dtype=torch.float32)
             L.check(lib.gm_conv2d_wgrad_grouped_bf16(ctypes.byref(d), G, dyd.data_ptr(), xd.data_ptr(), dw.data_ptr(),
-                                                      K * R * R * C, C, acc, scr.data_ptr(), need, L.stream_of(dev)),
+                                                      n, c_real, acc, scr.data_ptr(), need, L.stream_of(dev)),
                     "wgrad")
-            outs.append(dw)
+            assert torch.equal(dw[G * n:].cpu(), torch.full((64,), base)), f"{path}: written past the gradient"
+            outs.append(dw[:G * n].view(G, K, R, R, c_real))
         torch.cuda.synchronize()
     for gi in range(G):
         assert torch.equal(outs[0][gi].cpu(), refs[gi]), f"{path}: group {gi} plain"
