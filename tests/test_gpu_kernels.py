@@ -118,23 +118,25 @@ def test_spatial_reduce_and_scale(dev, dtype, layout, B, C, H, W):
     o = out.cpu().double()
     np.testing.assert_allclose(o[:, :C].numpy(), ref_sq.numpy(), rtol=1e-4, atol=1e-5)
     np.testing.assert_allclose(o[:, C:].numpy(), ref_da.numpy(), rtol=1e-4, atol=1e-4)
-    # scale (fwd) and apply (bwd)
-    s = torch.rand(B, C, generator=g)
-    a = torch.randn(B, C, generator=g)
-    Y, DX = torch.empty_like(X), torch.empty_like(X)
-    S, A = s.to(dev), a.to(dev)
+    # scale (fwd) and apply (bwd) on mmtmref's exact operands (x = m / 16, s = j / 1024, a = n / 8,
+    # alpha = 1/4, ties planted): every fp32 intermediate is exact, so the output equals the fp64 value,
+    # rounded once to bf16 - a truncating store, a second rounding or a wrong tie rule fails
+    import mmtmref as M
+    name = "bf16" if dtype == torch.bfloat16 else "f32"
+    so = M.scale_operands(B, C, HW, B * C + H)
+    X = so.x.view(B, C, H, W).to(dtype).to(dev).contiguous(memory_format=fmt)
+    Y, DX = torch.full_like(X, float("nan")), torch.full_like(X, float("nan"))
+    S, A = so.s.float().to(dev), so.a.float().to(dev)
     ops.channel_scale([dict(x=X, y=Y, C=C, HW=HW, s=S, ld_s=C)], B, dt, lay, dev)
-    ops.channel_scale([dict(x=DY, y=DX, C=C, HW=HW, s=S, ld_s=C, a=A, ld_a=C, alpha=1.0 / HW)],
+    ops.channel_scale([dict(x=X, y=DX, C=C, HW=HW, s=S, ld_s=C, a=A, ld_a=C, alpha=M.ALPHA)],
                       B, dt, lay, dev)
-    ref_y = (xf * s.double()[:, :, None, None]).to(dtype).double()
-    ref_dx = (df * s.double()[:, :, None, None] + a.double()[:, :, None, None] / HW).to(dtype).double()
-    tol = 1e-6 if dtype == torch.float32 else 8e-3
-    np.testing.assert_allclose(Y.cpu().double().numpy(), ref_y.numpy(), rtol=tol, atol=tol)
-    np.testing.assert_allclose(DX.cpu().double().numpy(), ref_dx.numpy(), rtol=tol, atol=tol)
+    want = lambda add, s0=False: M.store(M.scale_expected(so, add, s0), name).view(B, C, H, W)  # noqa: E731
+    assert torch.equal(Y.float().cpu(), want(False))
+    assert torch.equal(DX.float().cpu(), want(True))
     # broadcast row (curation): ld_s = 0
+    Y.fill_(float("nan"))
     ops.channel_scale([dict(x=X, y=Y, C=C, HW=HW, s=S, ld_s=0)], B, dt, lay, dev)
-    ref_b = (xf * s.double()[0][None, :, None, None]).to(dtype).double()
-    np.testing.assert_allclose(Y.cpu().double().numpy(), ref_b.numpy(), rtol=tol, atol=tol)
+    assert torch.equal(Y.float().cpu(), want(False, True))
 
 
 SCALE_CAP = 16384 * 256   # channel_scale_impl's grid cap: the vectors one trip of k_channel_scale covers
@@ -152,8 +154,8 @@ def test_channel_scale_second_trip(dev, dtype, shape, vec, layout):
     in the suite has about 0.4 M.  Each case exceeds the cap in vectors of `vec` elements (an odd
     element count forces the one-element form; HW % vec != 0 the NCHW form that looks up the
     channel per element), with and without the additive term, alone and as problem 0 of a
-    two-problem launch whose problem 1 then starts beyond the first trip.  Reference: the fp64
-    formula of test_spatial_reduce_and_scale, evaluated on the device, at its tolerances."""
+    two-problem launch whose problem 1 then starts beyond the first trip.  Operands: mmtmref's exact
+    recipe made on the device, so the output must be torch.equal to the exact value rounded once."""
     from greedy_multimodal_learning_amd import ops
     B, C, H, W = shape
     HW = H * W
@@ -167,20 +169,25 @@ def test_channel_scale_second_trip(dev, dtype, shape, vec, layout):
     g = torch.Generator(device=dev).manual_seed(B * C + H)
 
     def make(shp):
-        x = torch.randn(shp, device=dev, generator=g).to(dtype).contiguous(memory_format=fmt)
-        s = torch.rand(shp[0], shp[1], device=dev, generator=g)
-        a = torch.randn(shp[0], shp[1], device=dev, generator=g)
-        return x, s, a
+        """mmtmref's exact recipe, made on the device: x = m / 16 (1 <= |m| <= 255), s = j / 1024,
+        a = n / 8; channels c % 4 == 1 hold the ties (odd m in [87, 169], s = 1.5, a = 0)."""
+        b, c = shp[0], shp[1]
+        ri = lambda lo, hi, sh: torch.randint(lo, hi, sh, device=dev, generator=g)  # noqa: E731
+        tie = (torch.arange(c, device=dev) % 4 == 1).view(1, c, 1, 1)
+        m = torch.where(tie, ri(43, 85, shp) * 2 + 1, ri(1, 256, shp)) * (ri(0, 2, shp) * 2 - 1)
+        j = torch.where(tie[:, :, 0, 0], 1536, ri(0, 1025, (b, c)))
+        n = torch.where(tie[:, :, 0, 0], 0, ri(-64, 65, (b, c)))
+        x = (m.float() / 16).to(dtype).contiguous(memory_format=fmt)
+        return x, j.float() / 1024, n.float() / 8, (m, j, n)
 
-    def ref(x, s, a, hw):
-        r = x.double() * s.double()[:, :, None, None]
+    def ref(x, s, a, ints):
+        m, j, n = ints
+        num = m * j[:, :, None, None]                     # y 2^14 exactly, below 2^24: exact in fp32
         if a is not None:
-            r = r + a.double()[:, :, None, None] / hw
-        return r.to(dtype).double()
-
-    def close(y, r):
-        tol = 1e-6 if dtype == torch.float32 else 8e-3
-        return bool(((y.double() - r).abs() <= tol + tol * r.abs()).all())
+            num = num + 512 * n[:, :, None, None]
+        assert int(num.abs().max()) < 1 << 24
+        exact = (num.double() / 2.0 ** 14).float()
+        return exact.to(dtype), float((exact.to(dtype).float() != exact).float().mean())
 
     big, small = make(shape), make((B, 64, 3, 5))
     lay = ops.act_layout(big[0])
@@ -189,16 +196,18 @@ def test_channel_scale_second_trip(dev, dtype, shape, vec, layout):
     for add in (False, True):
         for nprob in (1, 2):
             probs, outs = [], []
-            for (x, s, a), (c, hw) in list(zip((big, small), ((C, HW), (64, 15))))[:nprob]:
+            for (x, s, a, ints), (c, hw) in list(zip((big, small), ((C, HW), (64, 15))))[:nprob]:
                 y = torch.full_like(x, float("nan"))
-                outs.append((x, s, a if add else None, hw, y))
+                outs.append((x, s, a if add else None, ints, y))
                 p = dict(x=x, y=y, C=c, HW=hw, s=s, ld_s=c)
                 if add:
-                    p.update(a=a, ld_a=c, alpha=1.0 / hw)
+                    p.update(a=a, ld_a=c, alpha=0.25)
                 probs.append(p)
             ops.channel_scale(probs, B, dt, lay, dev)
-            for i, (x, s, a, hw, y) in enumerate(outs):
-                assert close(y, ref(x, s, a, hw)), f"add={add} nprob={nprob} problem {i}"
+            for i, (x, s, a, ints, y) in enumerate(outs):
+                r, inexact = ref(x, s, a, ints)
+                assert torch.equal(y, r), f"add={add} nprob={nprob} problem {i}"
+                assert dtype == torch.float32 or inexact >= 0.25      # the store's rounding is under test
 
 
 def test_running_avg(dev):
