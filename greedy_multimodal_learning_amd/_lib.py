@@ -45,7 +45,7 @@ class Gemm(ctypes.Structure):
 class Tensor(ctypes.Structure):
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("n", ctypes.c_longlong),
                 ("offset", ctypes.c_longlong), ("group_mask", ctypes.c_uint),
-                ("pad", ctypes.c_uint)]
+                ("pgroup", ctypes.c_uint)]  # parameter-group index (gm_group_sumsq_pg only)
 
 
 EXPORTS = {
@@ -220,6 +220,20 @@ EXPORTS.update({
     "gm_group_sumsq_lr": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_float, c_void_p, c_float,
                                   c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
     "gm_lr_at": (c_int, [c_void_p, ctypes.c_longlong, c_void_p]),
+})
+
+SGD_MAX_PGROUPS = 16
+
+
+class SgdPGroup(ctypes.Structure):
+    """gm_sgd_pgroup: one parameter group's rate scale and weight decay (gm_group_sumsq_pg)."""
+    _fields_ = [("lr_scale", c_float), ("weight_decay", c_float)]
+
+
+EXPORTS.update({
+    "gm_group_sumsq_pg": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_float, c_void_p, c_void_p,
+                                  c_int, c_float, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "gm_sgd_pgroups_check": (c_int, [c_void_p, c_int]),
 })
 
 

@@ -125,11 +125,18 @@ class GroupNorms:
     with the same sums (the gradient's without the decay term).
     `sums(..., lr_state=)` launches gm_group_sumsq_lr: the same update in every form, with the
     rate read from a gm_lr_state in device memory, whose schedule the finalize launch advances.
+    `sums(..., lr_state=, pgroups=, nesterov=)` launches gm_group_sumsq_pg: each tensor's rate scale
+    and weight decay from its entry of the device group table `pgroups`, by the index
+    `pgroup_of(name)` written into the tensor table; optionally torch's Nesterov step.
     """
 
-    def __init__(self, named_params, branchnames, MMTMnames):
+    def __init__(self, named_params, branchnames, MMTMnames, pgroup_of=None):
         self.names = [n for n, _ in named_params]
         self.params = [p for _, p in named_params]
+        # parameter-group index per tensor (gm_tensor.pgroup; read by gm_group_sumsq_pg only)
+        self.pgroup = [0 if pgroup_of is None else int(pgroup_of(n)) for n in self.names]
+        if any(g < 0 for g in self.pgroup):
+            raise ValueError("group norms: a parameter-group index must be >= 0")
         self.ngroups = len(branchnames) + len(MMTMnames)
         self.masks = group_masks(self.names, branchnames, MMTMnames)
         self.total = int(sum(p.numel() for p in self.params))
@@ -173,7 +180,7 @@ class GroupNorms:
         off = 0
         for i, p in enumerate(self.params):
             tab[i] = L.Tensor(p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr(),
-                              p.numel(), off, self.masks[i], 0)
+                              p.numel(), off, self.masks[i], self.pgroup[i])
             off += p.numel()
         host = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8)
         self._table = host.to(self.device)
@@ -184,7 +191,7 @@ class GroupNorms:
             self._out = torch.empty(2 * self.ngroups, dtype=torch.float64, device=self.device)
 
     def sums(self, grad_scale=1.0, lr=0.0, gate=None, gate_n=False, momentum=0.0, weight_decay=0.0,
-             momentum_buffers=None, lr_state=None):
+             momentum_buffers=None, lr_state=None, pgroups=None, nesterov=False):
         """The step's group sums (and the fused SGD when lr != 0); gate (a device gm_gate_state /
         gm_gate_state_n tensor): the on-device gate's step runs in the same finalize launch.
         momentum / weight_decay (either non-zero: gm_group_sumsq_sgdm, whose update runs at
@@ -192,7 +199,11 @@ class GroupNorms:
         parallel to the parameters of zero-initialised fp32 tensors shaped and strided like
         them (None where the parameter has no gradient), advanced in place.
         lr_state (a device uint8 tensor holding a gm_lr_state; lr must stay 0): gm_group_sumsq_lr,
-        the update at the state's rate (it always runs) and the state advanced by one pass."""
+        the update at the state's rate (it always runs) and the state advanced by one pass.
+        pgroups (a contiguous device fp32 tensor [npgroups, 2] of (lr_scale, weight_decay) rows, a
+        gm_sgd_pgroup array; needs lr_state, and weight_decay must stay 0: the table owns it):
+        gm_group_sumsq_pg, every tensor updated with its group's rate and decay; nesterov (with
+        pgroups and a momentum > 0): torch's Nesterov step."""
         L.load()
         if not self.params[0].is_cuda:
             raise L.GreedyMMLError("group norms run on HIP devices only (no CPU fallback)")
@@ -203,6 +214,16 @@ class GroupNorms:
                     or lr_state.numel() < ctypes.sizeof(L.LrState) or lr_state.data_ptr() % 8):
                 raise L.GreedyMMLError("group norms: lr_state must be a contiguous, 8-byte aligned uint8 tensor "
                                        "holding a gm_lr_state on the parameters' device")
+        if pgroups is not None:
+            if lr_state is None or weight_decay != 0:
+                raise L.GreedyMMLError("group norms: pgroups need an lr_state and own the weight decay "
+                                       "(weight_decay must stay 0)")
+            if (pgroups.dtype != torch.float32 or pgroups.device != self.device or not pgroups.is_contiguous()
+                    or pgroups.dim() != 2 or pgroups.shape[1] != 2):
+                raise L.GreedyMMLError("group norms: pgroups must be a contiguous fp32 tensor [npgroups, 2] "
+                                       "(lr_scale, weight_decay) on the parameters' device")
+        elif nesterov:
+            raise L.GreedyMMLError("group norms: nesterov needs a parameter-group table (pgroups)")
         self._build()
         out = torch.empty(2 * self.ngroups, dtype=torch.float64, device=self.device)
         sgdm = momentum != 0 or weight_decay != 0
@@ -213,7 +234,12 @@ class GroupNorms:
         lib, table, stream = L.load(), self._table.data_ptr(), L.stream_of(self.device)
         sizes = (len(self.params), self.total, self.ngroups, float(grad_scale), float(lr))
         bufs = (out.data_ptr(), self._scratch.data_ptr(), self._scratch.numel())
-        if lr_state is not None:
+        if pgroups is not None:
+            name = "gm_group_sumsq_pg"
+            rc = lib.gm_group_sumsq_pg(table, mom, *sizes[:4], lr_state.data_ptr(), pgroups.data_ptr(),
+                                       pgroups.shape[0], float(momentum), int(bool(nesterov)), *bufs, L.ptr(gate),
+                                       int(bool(gate_n)), stream)
+        elif lr_state is not None:
             name = "gm_group_sumsq_lr"
             rc = lib.gm_group_sumsq_lr(table, mom, *sizes[:4], lr_state.data_ptr(), float(momentum),
                                        float(weight_decay), *bufs, L.ptr(gate), int(bool(gate_n)), stream)

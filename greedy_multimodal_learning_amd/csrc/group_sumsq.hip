@@ -14,11 +14,13 @@
 //
 // One of each: the update rule (sgd_update<upd>), the streaming loops and sums
 // (stream_segment<upd>), the chunk body per group-count form (chunk_sums, chunk_sums_runs) and
-// the host launch path (group_sumsq).  The update form - none, sgd, decay, mom - is a template
-// parameter all the way down; the eight __global__ kernels and the three entry points are
-// wrappers that choose it.  The device-rate wrappers (k_group_sumsq_dlr, gm_group_sumsq_lr) read
+// the host launch path (group_sumsq).  The update form - none, sgd, decay, mom, nest - is a template
+// parameter all the way down; the __global__ kernels and the entry points are wrappers that
+// choose it.  The device-rate wrappers (k_group_sumsq_dlr, gm_group_sumsq_lr) read
 // the learning rate from a gm_lr_state in device memory instead of an argument, and their
-// finalize advances its schedule (lr_rule.h): one captured step for every rate.
+// finalize advances its schedule (lr_rule.h): one captured step for every rate.  The parameter-group
+// wrappers (k_group_sumsq_pg, gm_group_sumsq_pg) also read each tensor's rate scale and weight decay
+// from a small device table, per segment.
 #include <cmath>
 
 #include "gm_common.h"
@@ -54,8 +56,11 @@ __device__ __forceinline__ int find_tensor(const gm_tensor* t, int nt, long long
 //   d = wd*w + g';  b' = mu*b + d;  w' = w - lr*b'
 // A zero-initialised buffer gives torch's first step (b' = d) exactly, so there is no step
 // counter.  The form is a compile-time choice: decay keeps b' = d in registers (no buffer
-// stream), sgd is d = g' as well (w' = w - lr*g'), none writes nothing.
-enum class upd { none, sgd, decay, mom };
+// stream), sgd is d = g' as well (w' = w - lr*g'), none writes nothing.  nest is mom with torch's
+// Nesterov step: w' = w - lr*(mu*b' + d), one more fma.
+enum class upd { none, sgd, decay, mom, nest };
+
+constexpr bool has_buffer(upd u) { return u == upd::mom || u == upd::nest; }
 
 struct sgdm_args {
     float gscale, lr, mu, wd;
@@ -65,15 +70,15 @@ template <upd U>
 __device__ __forceinline__ float sgd_update(float w, float g, float& b, const sgdm_args& h) {
     if (U == upd::sgd) return fmaf(-h.lr, g, w);
     const float d = fmaf(h.wd, w, g);
-    b = U == upd::mom ? fmaf(h.mu, b, d) : d;
-    return fmaf(-h.lr, b, w);
+    b = has_buffer(U) ? fmaf(h.mu, b, d) : d;
+    return fmaf(-h.lr, U == upd::nest ? fmaf(h.mu, b, d) : b, w);
 }
 
 // Streams elements [tb, te) of one tensor: accumulates w^2 and g'^2 into sw, sg and applies the
-// update in place; mb: the tensor's momentum buffer (upd::mom only).  The sums take w before the
+// update in place; mb: the tensor's momentum buffer (upd::mom and nest only).  The sums take w before the
 // update and g' without the decay term, in one order for every form: they are bit-identical
 // between the forms.  16-byte path: p, g (and mb) congruent mod 16, else the scalar loop.  HBM
-// bytes per element: 8 (none), 12 (sgd, decay), 20 (mom: + read and write mb).
+// bytes per element: 8 (none), 12 (sgd, decay), 20 (mom, nest: + read and write mb).
 // An entry without a gradient is summed for w^2 only and not written (torch: grad is None).  The
 // sgd form tests for it inline; decay and mom hand it to the sums-only form up front, and so know
 // the gradient present below at compile time (inline it costs upd::mom 5 VGPRs and a wave per
@@ -82,7 +87,7 @@ __device__ __forceinline__ float sgd_update(float w, float g, float& b, const sg
 template <upd U>
 __device__ __forceinline__ void stream_segment(const gm_tensor& T, float* __restrict__ mb, long long tb,
                                                long long te, const sgdm_args& h, float& sw, float& sg) {
-    constexpr bool MOM = U == upd::mom, EARLY = U == upd::decay || U == upd::mom;
+    constexpr bool MOM = has_buffer(U), EARLY = U == upd::decay || MOM;
     if (EARLY && (T.grad == nullptr || (MOM && mb == nullptr))) {
         stream_segment<upd::none>(T, nullptr, tb, te, h, sw, sg);
         return;
@@ -155,11 +160,35 @@ __device__ __forceinline__ void stream_segment(const gm_tensor& T, float* __rest
     for (long long i = head + nv * 4 + threadIdx.x; i < te; i += 256) one(i);
 }
 
+// The hyper-parameters of a tensor segment, as the chunk bodies below ask for them (hs(T)): one
+// sgdm_args for the whole pass, or per parameter group.  A segment is uniform across the workgroup,
+// so either way they sit in scalar registers.
+struct uniform_args {
+    sgdm_args h;
+    __device__ __forceinline__ const sgdm_args& operator()(const gm_tensor&) const { return h; }
+};
+
+// gm_group_sumsq_pg: rate scale and weight decay from the tensor's entry of the device group table
+// (index clamped to the table); the group's rate is the fp64 product rounded once
+struct pgroup_args {
+    float gscale, lr, mu;
+    const gm_sgd_pgroup* __restrict__ pg;
+    unsigned last;  // npgroups - 1
+    __device__ __forceinline__ sgdm_args operator()(const gm_tensor& T) const {
+        const gm_sgd_pgroup e = pg[min(T.pgroup, last)];
+        // (the fp64 product is vector arithmetic; readfirstlane puts the uniform result back into a
+        // scalar register - left in a VGPR it costs upd::mom 6 VGPRs and its fourth wave per SIMD)
+        const float lr_g = (float)((double)lr * (double)e.lr_scale);
+        return {gscale, __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lr_g))), mu,
+                e.weight_decay};
+    }
+};
+
 // One workgroup's chunk, <= 8 groups: per-thread fp64 sums per group, folded over the waves in
-// fixed order into one row.  mom: the tensors' buffers (upd::mom only)
-template <upd U, int MG>
+// fixed order into one row.  mom: the tensors' buffers (upd::mom and nest only)
+template <upd U, int MG, class H>
 __device__ __forceinline__ void chunk_sums(const gm_tensor* __restrict__ tab, float* const* __restrict__ mom,
-                                           int nt, long long total, int ngroups, const sgdm_args& h,
+                                           int nt, long long total, int ngroups, const H& hs,
                                            long long chunk, double* __restrict__ rows) {
     __shared__ double sred[4][2 * MG];
     const long long e0 = (long long)blockIdx.x * chunk;
@@ -174,7 +203,7 @@ __device__ __forceinline__ void chunk_sums(const gm_tensor* __restrict__ tab, fl
         const long long tb = e - T.offset;                       // first local element
         const long long te = min(T.n, e1 - T.offset);            // end (exclusive)
         float sw = 0.f, sg = 0.f;
-        stream_segment<U>(T, U == upd::mom ? mom[ti] : nullptr, tb, te, h, sw, sg);
+        stream_segment<U>(T, has_buffer(U) ? mom[ti] : nullptr, tb, te, hs(T), sw, sg);
         const unsigned m = T.group_mask;
 #pragma unroll
         for (int g = 0; g < MG; ++g)
@@ -219,9 +248,9 @@ __device__ __forceinline__ void flush_run(double& aw, double& ag, unsigned mask,
     ag = 0.0;
 }
 
-template <upd U>
+template <upd U, class H>
 __device__ __forceinline__ void chunk_sums_runs(const gm_tensor* __restrict__ tab, float* const* __restrict__ mom,
-                                                int nt, long long total, int ngroups, const sgdm_args& h,
+                                                int nt, long long total, int ngroups, const H& hs,
                                                 long long chunk, double* __restrict__ rows) {
     __shared__ double sred[4][2];
     __shared__ double acc[2 * kMaxGroups];
@@ -241,7 +270,7 @@ __device__ __forceinline__ void chunk_sums_runs(const gm_tensor* __restrict__ ta
         const long long tb = e - T.offset;
         const long long te = min(T.n, e1 - T.offset);
         float sw = 0.f, sg = 0.f;
-        stream_segment<U>(T, U == upd::mom ? mom[ti] : nullptr, tb, te, h, sw, sg);
+        stream_segment<U>(T, has_buffer(U) ? mom[ti] : nullptr, tb, te, hs(T), sw, sg);
         aw += (double)sw;
         ag += (double)sg;
         e = T.offset + te;
@@ -257,14 +286,16 @@ template <bool SGD, int MG>
 __global__ __launch_bounds__(256) void k_group_sumsq(const gm_tensor* __restrict__ tab, int nt,
                                                      long long total, int ngroups, float gscale,
                                                      float lr, long long chunk, double* __restrict__ rows) {
-    chunk_sums<SGD ? upd::sgd : upd::none, MG>(tab, nullptr, nt, total, ngroups, {gscale, lr, 0.f, 0.f}, chunk, rows);
+    chunk_sums<SGD ? upd::sgd : upd::none, MG>(tab, nullptr, nt, total, ngroups, uniform_args{{gscale, lr, 0.f, 0.f}},
+                                               chunk, rows);
 }
 
 template <bool SGD>
 __global__ __launch_bounds__(256) void k_group_sumsq_runs(const gm_tensor* __restrict__ tab, int nt,
                                                           long long total, int ngroups, float gscale,
                                                           float lr, long long chunk, double* __restrict__ rows) {
-    chunk_sums_runs<SGD ? upd::sgd : upd::none>(tab, nullptr, nt, total, ngroups, {gscale, lr, 0.f, 0.f}, chunk, rows);
+    chunk_sums_runs<SGD ? upd::sgd : upd::none>(tab, nullptr, nt, total, ngroups, uniform_args{{gscale, lr, 0.f, 0.f}},
+                                                chunk, rows);
 }
 
 template <bool MOM, int MG>
@@ -272,7 +303,7 @@ __global__ __launch_bounds__(256) void k_group_sumsq_sgdm(const gm_tensor* __res
                                                           float* const* __restrict__ mom, int nt, long long total,
                                                           int ngroups, sgdm_args h, long long chunk,
                                                           double* __restrict__ rows) {
-    chunk_sums<MOM ? upd::mom : upd::decay, MG>(tab, mom, nt, total, ngroups, h, chunk, rows);
+    chunk_sums<MOM ? upd::mom : upd::decay, MG>(tab, mom, nt, total, ngroups, uniform_args{h}, chunk, rows);
 }
 
 template <bool MOM>
@@ -280,7 +311,7 @@ __global__ __launch_bounds__(256) void k_group_sumsq_sgdm_runs(const gm_tensor* 
                                                                float* const* __restrict__ mom, int nt,
                                                                long long total, int ngroups, sgdm_args h,
                                                                long long chunk, double* __restrict__ rows) {
-    chunk_sums_runs<MOM ? upd::mom : upd::decay>(tab, mom, nt, total, ngroups, h, chunk, rows);
+    chunk_sums_runs<MOM ? upd::mom : upd::decay>(tab, mom, nt, total, ngroups, uniform_args{h}, chunk, rows);
 }
 
 // The device-rate forms: the rate is *lrs, read once per workgroup (a uniform load that ends in a
@@ -291,7 +322,7 @@ __global__ __launch_bounds__(256) void k_group_sumsq_dlr(const gm_tensor* __rest
                                                          int ngroups, float gscale,
                                                          const gm_lr_state* __restrict__ lrs, float mu, float wd,
                                                          long long chunk, double* __restrict__ rows) {
-    chunk_sums<U, MG>(tab, mom, nt, total, ngroups, {gscale, lrs->lr, mu, wd}, chunk, rows);
+    chunk_sums<U, MG>(tab, mom, nt, total, ngroups, uniform_args{{gscale, lrs->lr, mu, wd}}, chunk, rows);
 }
 
 template <upd U>
@@ -301,7 +332,31 @@ __global__ __launch_bounds__(256) void k_group_sumsq_dlr_runs(const gm_tensor* _
                                                               const gm_lr_state* __restrict__ lrs, float mu,
                                                               float wd, long long chunk,
                                                               double* __restrict__ rows) {
-    chunk_sums_runs<U>(tab, mom, nt, total, ngroups, {gscale, lrs->lr, mu, wd}, chunk, rows);
+    chunk_sums_runs<U>(tab, mom, nt, total, ngroups, uniform_args{{gscale, lrs->lr, mu, wd}}, chunk, rows);
+}
+
+// The parameter-group forms (decay, mom, nest): the device-rate kernels with each segment's rate
+// scale and weight decay read from the group table pg[0..npg) by the tensor's index (pgroup_args).
+template <upd U, int MG>
+__global__ __launch_bounds__(256) void k_group_sumsq_pg(const gm_tensor* __restrict__ tab,
+                                                        float* const* __restrict__ mom, int nt, long long total,
+                                                        int ngroups, float gscale,
+                                                        const gm_lr_state* __restrict__ lrs, float mu,
+                                                        const gm_sgd_pgroup* __restrict__ pg, int npg,
+                                                        long long chunk, double* __restrict__ rows) {
+    chunk_sums<U, MG>(tab, mom, nt, total, ngroups, pgroup_args{gscale, lrs->lr, mu, pg, (unsigned)(npg - 1)}, chunk,
+                      rows);
+}
+
+template <upd U>
+__global__ __launch_bounds__(256) void k_group_sumsq_pg_runs(const gm_tensor* __restrict__ tab,
+                                                             float* const* __restrict__ mom, int nt,
+                                                             long long total, int ngroups, float gscale,
+                                                             const gm_lr_state* __restrict__ lrs, float mu,
+                                                             const gm_sgd_pgroup* __restrict__ pg, int npg,
+                                                             long long chunk, double* __restrict__ rows) {
+    chunk_sums_runs<U>(tab, mom, nt, total, ngroups, pgroup_args{gscale, lrs->lr, mu, pg, (unsigned)(npg - 1)}, chunk,
+                       rows);
 }
 
 // 1024 threads stream the [nrows][w] row block as one flat array with fully coalesced
@@ -391,9 +446,16 @@ static auto dlr_kernel(bool few) {
     return few ? k_group_sumsq_dlr<U, 8> : k_group_sumsq_dlr_runs<U>;
 }
 
+template <upd U>
+static auto pg_kernel(bool few) {
+    return few ? k_group_sumsq_pg<U, 8> : k_group_sumsq_pg_runs<U>;
+}
+
+// pg (with lrs): the device group table of gm_group_sumsq_pg (null: h.wd for every tensor)
 static int group_sumsq(const gm_tensor* table, float* const* mom, int nt, long long total, int ngroups,
                        const sgdm_args& h, upd form, double* out, void* scratch, size_t scratch_bytes, void* gate,
-                       int gate_n, void* stream, gm_lr_state* lrs = nullptr) {
+                       int gate_n, void* stream, gm_lr_state* lrs = nullptr, const gm_sgd_pgroup* pg = nullptr,
+                       int npg = 0) {
     // (main, bypass) groups per branch: 4 for the two-branch gate, 2 nb for the N-branch one (nb in
     // the state: the rule reads 4 nb sums)
     GM_REQUIRE(!gate || (gate_n ? (ngroups >= 4 && ngroups % 2 == 0) : ngroups == 4),
@@ -410,7 +472,11 @@ static int group_sumsq(const gm_tensor* table, float* const* mom, int nt, long l
     double* rows = (double*)scratch;
     const bool few = ngroups <= 8;  // else the N-branch gates (C5: 12 branches -> 24 groups)
     const bool plain = form == upd::none || form == upd::sgd;
-    if (lrs) {
+    if (pg) {
+        const auto k = form == upd::nest ? pg_kernel<upd::nest>(few)
+                                         : (form == upd::mom ? pg_kernel<upd::mom>(few) : pg_kernel<upd::decay>(few));
+        k<<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h.gscale, lrs, h.mu, pg, npg, chunk, rows);
+    } else if (lrs) {
         const auto k = form == upd::sgd ? dlr_kernel<upd::sgd>(few)
                                         : (form == upd::mom ? dlr_kernel<upd::mom>(few) : dlr_kernel<upd::decay>(few));
         k<<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h.gscale, lrs, h.mu, h.wd, chunk, rows);
@@ -425,7 +491,8 @@ static int group_sumsq(const gm_tensor* table, float* const* mom, int nt, long l
                            : (mo ? k_group_sumsq_sgdm_runs<true> : k_group_sumsq_sgdm_runs<false>);
         k<<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h, chunk, rows);
     }
-    int rc = check_launch(lrs ? "k_group_sumsq_dlr" : (plain ? "k_group_sumsq" : "k_group_sumsq_sgdm"));
+    int rc = check_launch(pg ? "k_group_sumsq_pg"
+                             : (lrs ? "k_group_sumsq_dlr" : (plain ? "k_group_sumsq" : "k_group_sumsq_sgdm")));
     if (rc) return rc;
     if (lrs) k_group_finalize_lr<<<1, kFinT, 0, st>>>(rows, nb, ngroups, out, gate, gate && gate_n ? 1 : 0, lrs);
     else k_group_finalize<<<1, kFinT, 0, st>>>(rows, nb, ngroups, out, gate, gate && gate_n ? 1 : 0);
@@ -471,6 +538,36 @@ extern "C" int gm_group_sumsq_lr(const gm_tensor* table, float* const* mom, int 
     const upd form = mom ? upd::mom : (weight_decay != 0.f ? upd::decay : upd::sgd);
     return group_sumsq(table, mom, nt, total, ngroups, {gscale, 0.f, momentum, weight_decay}, form, out, scratch,
                        scratch_bytes, gate, gate_n, stream, lr);
+}
+
+extern "C" int gm_group_sumsq_pg(const gm_tensor* table, float* const* mom, int nt, long long total, int ngroups,
+                                 float gscale, gm_lr_state* lr, const gm_sgd_pgroup* pgroups, int npgroups,
+                                 float momentum, int nesterov, double* out, void* scratch, size_t scratch_bytes,
+                                 void* gate, int gate_n, void* stream) {
+    GM_REQUIRE(lr, "group_sumsq_pg: null lr state");
+    GM_REQUIRE(pgroups, "group_sumsq_pg: null parameter-group table");
+    GM_REQUIRE(npgroups >= 1 && npgroups <= GM_SGD_MAX_PGROUPS, "group_sumsq_pg: npgroups must be 1..%d",
+               GM_SGD_MAX_PGROUPS);
+    GM_REQUIRE(std::isfinite(momentum) && momentum >= 0.f, "group_sumsq_pg: momentum must be finite and >= 0");
+    GM_REQUIRE(!nesterov || momentum > 0.f, "group_sumsq_pg: nesterov requires a momentum > 0");
+    GM_REQUIRE((mom != nullptr) == (momentum != 0.f),
+               "group_sumsq_pg: momentum buffers must be given if and only if momentum != 0");
+    const upd form = mom ? (nesterov ? upd::nest : upd::mom) : upd::decay;
+    return group_sumsq(table, mom, nt, total, ngroups, {gscale, 0.f, momentum, 0.f}, form, out, scratch,
+                       scratch_bytes, gate, gate_n, stream, lr, pgroups, npgroups);
+}
+
+extern "C" int gm_sgd_pgroups_check(const gm_sgd_pgroup* host, int npgroups) {
+    GM_REQUIRE(host, "sgd_pgroups_check: null table");
+    GM_REQUIRE(npgroups >= 1 && npgroups <= GM_SGD_MAX_PGROUPS, "sgd_pgroups_check: npgroups must be 1..%d",
+               GM_SGD_MAX_PGROUPS);
+    for (int i = 0; i < npgroups; ++i) {
+        GM_REQUIRE(std::isfinite(host[i].lr_scale) && host[i].lr_scale >= 0.f,
+                   "sgd_pgroups_check: group %d: lr_scale must be finite and >= 0", i);
+        GM_REQUIRE(std::isfinite(host[i].weight_decay) && host[i].weight_decay >= 0.f,
+                   "sgd_pgroups_check: group %d: weight_decay must be finite and >= 0", i);
+    }
+    return 0;
 }
 
 extern "C" int gm_lr_at(const gm_lr_state* s, long long t, float* lr_out) {

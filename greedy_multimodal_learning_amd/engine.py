@@ -19,7 +19,9 @@ re-organised for the hardware:
   the only host sync per step is the 8-double copy the gate needs for its
   decision (the decision applies to the NEXT forward, as in the reference);
   with `momentum` / `weight_decay` the same pass applies torch.optim.SGD's rule
-  (`gm_group_sumsq_sgdm`) on a third flat buffer, the momentum buffers;
+  (`gm_group_sumsq_sgdm`) on a third flat buffer, the momentum buffers; with
+  `param_groups` / `nesterov` (`gm_group_sumsq_pg`) each parameter's rate scale and
+  weight decay come from a small device table and the step may be Nesterov's;
 * the trunk runs in bf16 (autocast) on channels_last activations; master
   weights, gradients, the MMTM FC chain and all reductions stay fp32;
 * `graphs=True`: after one eager step, each curation setting
@@ -263,9 +265,21 @@ class BalancedStep:
     def __init__(self, model, lr=0.1, gate=None, compute_dtype=torch.bfloat16, channels_last=True,
                  process_group=None, bucket_mb=25.0, branchnames=("net_view_0", "net_view_1"),
                  MMTMnames=("visual", "skeleton"), graphs=False, device_gate=None, dp_buckets=None,
-                 mmtm_excite=None, f32_contraction=None, momentum=0.0, weight_decay=0.0, lr_schedule=None):
+                 mmtm_excite=None, f32_contraction=None, momentum=0.0, weight_decay=0.0, lr_schedule=None,
+                 param_groups=None, nesterov=False):
         import math
         self.model = model
+        # param_groups (a param_groups.ParamGroups) / nesterov: the update runs through
+        # gm_group_sumsq_pg - each parameter's rate scale and weight decay from a small device table
+        # (self.pgroups, made below, before any capture), optionally torch's Nesterov step.  Either
+        # implies a device rate: without a schedule the engine holds one itself (kind "held", so
+        # `step.lr = x` stays a 4-byte fill).  Both off (the default): nothing of this exists.
+        self.param_groups, self.nesterov = param_groups, bool(nesterov)
+        if self.nesterov and not float(momentum) > 0.0:
+            raise ValueError("BalancedStep: nesterov=True requires a momentum > 0")
+        if (param_groups is not None or self.nesterov) and lr_schedule is None:
+            from .lr_schedule import LRSchedule
+            lr_schedule = LRSchedule("held", lr)
         # lr_schedule (an lr_schedule.LRSchedule; None: the rate is the `lr` argument of the update
         # kernels and part of every captured graph's key): the rate lives in a device gm_lr_state
         # (self.lr_state, made below, before any capture), the update kernels read it there and the
@@ -310,7 +324,21 @@ class BalancedStep:
         if self.device.type == "cuda":
             from . import vtrunk
             vtrunk._wgrad_stream(self.device)  # (the stacked trunk's weight-gradient stream, likewise)
-        self.norms = GroupNorms(named, list(branchnames), list(MMTMnames))
+        self.pgroups = None  # device fp32 [npgroups, 2]: (lr_scale, weight_decay) per parameter group
+        self._pgroups_host = None
+        if param_groups is not None or self.nesterov:
+            from .param_groups import ParamGroups, pack_table
+            groups = param_groups if param_groups is not None else ParamGroups()
+            if groups.weight_decay is not None and self.weight_decay not in (0.0, groups.weight_decay):
+                raise ValueError(f"BalancedStep: weight_decay={self.weight_decay!r} and the parameter groups' "
+                                 f"own default {groups.weight_decay!r} disagree")
+            import struct
+            raw = pack_table(groups.table(self.weight_decay))  # (the library's host-side check)
+            self._pgroups_host = [list(row) for row in struct.iter_unpack("ff", raw)]  # as the device holds them
+            self.pgroups = torch.frombuffer(bytearray(raw), dtype=torch.float32).view(-1, 2).to(self.device)
+            self.norms = GroupNorms(named, list(branchnames), list(MMTMnames), pgroup_of=groups.group_of)
+        else:
+            self.norms = GroupNorms(named, list(branchnames), list(MMTMnames))
         if lr_schedule is not None:
             self.lr_state = torch.frombuffer(bytearray(lr_schedule.pack(0)), dtype=torch.uint8).to(self.device)
         # one flat zero momentum buffer at FlatParams' offsets (so co-aligned with the parameter
@@ -464,7 +492,10 @@ class BalancedStep:
         """The fused norms+SGD pass; with the on-device gate its step rides in the same finalize
         launch (gm_group_sumsq_gate)."""
         kw = {}
-        if self.momentum != 0.0 or self.weight_decay != 0.0:  # gm_group_sumsq_sgdm
+        if self.pgroups is not None:  # gm_group_sumsq_pg: rate scale and weight decay from the group table
+            kw = dict(pgroups=self.pgroups, nesterov=self.nesterov, momentum=self.momentum,
+                      momentum_buffers=self._mom_bufs)
+        elif self.momentum != 0.0 or self.weight_decay != 0.0:  # gm_group_sumsq_sgdm
             kw = dict(momentum=self.momentum, weight_decay=self.weight_decay, momentum_buffers=self._mom_bufs)
         if self.device_gate:
             kw.update(gate=self.gate_state, gate_n=self.gate_n)
@@ -532,6 +563,126 @@ class BalancedStep:
             O, I, kh, kw = p.shape
             return view.view(O, kh, kw, I).permute(0, 3, 1, 2)
         return view.view(p.shape)
+
+    # ---------------- parameter groups ----------------
+    def _need_groups(self, what):
+        if self.pgroups is None:
+            raise ValueError(f"BalancedStep.{what}: no parameter groups (param_groups=None, nesterov=False)")
+
+    def param_group_of(self, p):
+        """The group index of parameter p (a tensor of the model, or its name)."""
+        self._need_groups("param_group_of")
+        if isinstance(p, str):
+            return self.norms.pgroup[self.norms.names.index(p)]
+        for q, g in zip(self.norms.params, self.norms.pgroup):
+            if q is p:
+                return g
+        raise KeyError("param_group_of: not a parameter of this engine's model")
+
+    def param_group(self, i):
+        """Group i as {'lr_scale', 'weight_decay', 'lr'} from the host mirror of the device table
+        (no sync); lr: the group's rate at the next step, the fp64 product rounded to fp32."""
+        self._need_groups("param_group")
+        from .lr_schedule import _f32
+        s, wd = self._pgroups_host[i]
+        return {"lr_scale": s, "weight_decay": wd, "lr": _f32(_f32(self.lr) * s)}
+
+    def set_param_group(self, i, lr_scale=None, weight_decay=None):
+        """Change group i's rate scale and / or weight decay from the next step on: one
+        stream-ordered 8-byte fill of the device entry, which the captured step reads - no host
+        sync, no re-capture.  Under data parallelism every rank makes the same call."""
+        self._need_groups("set_param_group")
+        import struct
+        from .param_groups import _value
+        i = int(i)
+        if not 0 <= i < len(self._pgroups_host):
+            raise IndexError(f"set_param_group: group {i} of {len(self._pgroups_host)}")
+        row = self._pgroups_host[i]
+        new = [row[0] if lr_scale is None else _value("lr_scale", lr_scale),
+               row[1] if weight_decay is None else _value("weight_decay", weight_decay)]
+        bits = struct.pack("ff", *new)  # (OverflowError beyond fp32's range)
+        new = list(struct.unpack("ff", bits))  # as the device holds them: fp32
+        self.pgroups.view(torch.int64)[i].fill_(struct.unpack("q", bits)[0])
+        self._pgroups_host[i] = new
+
+    def torch_param_groups(self):
+        """The param groups a torch.optim.SGD over this engine's model holds: one dict per
+        non-empty engine group, in group order, its parameters in model.parameters() order, with
+        the group's lr (the step's rate x lr_scale), weight_decay, momentum and nesterov.  Without
+        parameter groups: one group of everything.  load_optimizer_state reads a state_dict's
+        parameter indices in this order."""
+        params = list(self.model.parameters())
+        common = {"momentum": self.momentum, "nesterov": self.nesterov}
+        if self.pgroups is None:
+            return [dict(common, params=params, lr=self.lr, weight_decay=self.weight_decay)]
+        by_id = {id(q): g for q, g in zip(self.norms.params, self.norms.pgroup)}
+        out = []
+        for i, (scale, wd) in enumerate(self._pgroups_host):
+            ps = [p for p in params if by_id[id(p)] == i]
+            if ps:
+                out.append(dict(common, params=ps, lr=self.lr * scale, weight_decay=wd))
+        return out
+
+    def load_optimizer_state(self, sd):
+        """Continue from a checkpoint's 'optimizer' entry: `sd` is the state_dict() of a
+        torch.optim.SGD built over torch_param_groups(), as training_loop saves it.  Every
+        `momentum_buffer` is copied into the engine's flat momentum buffer (through
+        momentum_buffer(p): a channels-last parameter's buffer is the channels-last view).  Raises
+        ValueError - before anything is copied - on a missing or mis-shaped buffer, on groups that
+        are not the engine's (sizes, indices) and on a group whose momentum, nesterov, dampening,
+        weight decay or ratio of rates disagrees with the engine's.  Valid before the first step and
+        between steps: captured graphs update the flat buffer in place.  The rate itself is not
+        taken from `sd` (step.lr / the schedule own it)."""
+        import math
+        mine, theirs = self.torch_param_groups(), sd["param_groups"]
+        k = 0
+        for j, g in enumerate(mine):
+            n = len(g["params"])
+            if j >= len(theirs) or list(theirs[j]["params"]) != list(range(k, k + n)):
+                raise ValueError(f"load_optimizer_state: the state_dict's param groups are not the engine's "
+                                 f"(group {j}: {n} parameters from index {k})")
+            k += n
+        if len(theirs) != len(mine):
+            raise ValueError(f"load_optimizer_state: {len(theirs)} param groups, the engine has {len(mine)}")
+
+        def close(a, b):
+            return math.isclose(float(a), float(b), rel_tol=1e-6, abs_tol=1e-12)
+
+        base = None  # one rate behind all groups: lr_j / scale_j is the same for every j
+        for j, (g, t) in enumerate(zip(mine, theirs)):
+            for key in ("momentum", "weight_decay"):
+                if not close(t.get(key, 0.0), g[key]):
+                    raise ValueError(f"load_optimizer_state: group {j}: {key} {t.get(key)!r} != the engine's "
+                                     f"{g[key]!r}")
+            if bool(t.get("nesterov", False)) != self.nesterov:
+                raise ValueError(f"load_optimizer_state: group {j}: nesterov {t.get('nesterov')!r} != the engine's "
+                                 f"{self.nesterov!r}")
+            if float(t.get("dampening", 0.0)) != 0.0:
+                raise ValueError("load_optimizer_state: dampening is not supported")
+            if g["lr"] > 0.0 and self.lr > 0.0:
+                ratio = float(t["lr"]) / (g["lr"] / self.lr)
+                base = ratio if base is None else base
+                if not close(ratio, base):
+                    raise ValueError(f"load_optimizer_state: group {j}: lr {t['lr']!r} is not in the engine's "
+                                     f"ratio to the other groups' (base rate {base!r})")
+        if self.flat_momentum is None:
+            if any(st.get("momentum_buffer") is not None for st in sd["state"].values()):
+                raise ValueError("load_optimizer_state: the state_dict holds momentum buffers, the engine has "
+                                 "momentum 0")
+            return
+        params = [p for g in mine for p in g["params"]]
+        bufs = []
+        for k, p in enumerate(params):
+            b = sd["state"].get(k, {}).get("momentum_buffer")
+            if b is None:
+                raise ValueError(f"load_optimizer_state: no momentum_buffer for parameter {k}")
+            if tuple(b.shape) != tuple(p.shape):
+                raise ValueError(f"load_optimizer_state: parameter {k}: momentum_buffer of shape {tuple(b.shape)} "
+                                 f"for a parameter of shape {tuple(p.shape)}")
+            bufs.append(b)
+        with torch.no_grad():
+            for p, b in zip(params, bufs):
+                self.momentum_buffer(p).copy_(b.to(device=self.device, dtype=torch.float32))
 
     def gate_struct(self):
         """The device gate state as its ctypes mirror (GateState / GateStateN); a host sync."""

@@ -184,7 +184,8 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
                   custom_callbacks=[], checkpoint_monitor="val_acc", n_epochs=100, verbose=True, nummodalities=2,
                   compute_dtype="fp32", graphs=True, f32_contraction="exact", eval_engine="modules",
                   eval_f32_trunk="modules", fused_momentum=False, lr_schedule=None, lr_warmup_steps=0,
-                  lr_warmup_start=0.0, lr_milestones=(), lr_gamma=0.1, lr_total_steps=None, lr_min=0.0):
+                  lr_warmup_start=0.0, lr_milestones=(), lr_gamma=0.1, lr_total_steps=None, lr_min=0.0,
+                  param_groups=None, nesterov=False, optimizer_state_from=None):
     """Reference src/training_loop.py:86-143 + Model_.train_loop (src/framework.py:
     250-330) on the fused engine.  `optimizer` is the (lr, momentum, wd) triple of the
     reference's SGD (a torch SGD over the model's parameters holds the learning rate and
@@ -213,7 +214,18 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
     re-capture); "multistep" and "cosine" run on the device and refuse ReduceLROnPlateau_PyTorch
     (two owners of one rate).  With a schedule each epoch's logs get `lr` (the rate after the
     epoch's last step), the checkpoint's optimizer carries that rate and the checkpoint an
-    `lr_schedule` entry {params, step}."""
+    `lr_schedule` entry {params, step}.
+    `param_groups` (None; the string "no_decay_norm_bias": no weight decay on BatchNorm parameters
+    and biases; or a tuple of (substrings, lr_scale, weight_decay) triples, param_groups.ParamGroups'
+    rules) and `nesterov` run the update through the engine's parameter-group pass
+    (BalancedStep(param_groups=, nesterov=)); the never-stepped torch SGD is then built with the
+    same groups - per-group lr, weight_decay, nesterov - so a checkpoint's 'optimizer' entry holds
+    what a real torch run would.  `optimizer_state_from` (a checkpoint path): its 'optimizer' entry
+    goes through BalancedStep.load_optimizer_state (the caller has loaded the checkpoint's 'model'
+    entry into `model`) - the momentum buffers continue; the gate's accumulators and curation state
+    and the MMTM sites' running averages and step counters (plain attributes, not part of
+    model.state_dict()) are NOT resumed.  All three follow fused_momentum's rule for a
+    non-zero momentum or weight decay."""
     import math
 
     from .engine import BalancedStep
@@ -243,12 +255,30 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
         raise ValueError("at most one gating callback")
     gate = gates[0] if gates else None
     cdt = _DTYPES[compute_dtype]
+    from .param_groups import from_config
+    groups = from_config(param_groups, wd)
     step = BalancedStep(model, lr=lr, gate=gate, compute_dtype=cdt, channels_last=True, graphs=graphs,
                         f32_contraction=f32_contraction_arg(cdt, f32_contraction), momentum=momentum,
-                        weight_decay=wd, lr_schedule=sched)
+                        weight_decay=wd, lr_schedule=sched, param_groups=groups, nesterov=nesterov)
     # the reference's optimizer object (never stepped: the engine's fused pass applies the
     # update with the learning rate read from it)
-    opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=wd)
+    # (with parameter groups: the same groups - per-group lr, weight_decay, nesterov - so the
+    # checkpoints' 'optimizer' entry holds what a real torch run would)
+    if step.pgroups is None:
+        opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=wd)
+        lr_scales = [1.0]
+    else:
+        tgroups = step.torch_param_groups()
+        opt = torch.optim.SGD(tgroups, lr=lr, momentum=momentum, weight_decay=wd, nesterov=bool(nesterov))
+        lr_scales = [step.param_group(step.param_group_of(g["params"][0]))["lr_scale"] for g in tgroups]
+    # the torch group whose lr is the step's rate itself (ReduceLROnPlateau_PyTorch scales every
+    # group alike): one of scale 1
+    lr_from = next((j for j, s in enumerate(lr_scales) if s == 1.0), None)
+    if lr_from is None:
+        raise ValueError("training_loop.param_groups: at least one parameter must stay at lr_scale 1 "
+                         "(the group the host reads the step's rate from)")
+    if optimizer_state_from is not None:
+        step.load_optimizer_state(torch.load(optimizer_state_from, map_location="cpu")["optimizer"])
     estep = eval_engine_arg(model, cdt, eval_engine, graphs, f32_trunk=eval_f32_trunk)
     flags = step.flags  # the gate's model_pytoune; every other callback shares it
     flags.stop_training = False
@@ -284,7 +314,7 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
             for c in others:
                 c.on_batch_begin(bi + 1, {})
             if sched is None or not sched.device_run:  # (held: a 4-byte fill when the rate changed)
-                step.lr = float(opt.param_groups[0]["lr"])
+                step.lr = float(opt.param_groups[lr_from]["lr"])
             loss = step(x, y)
             outs = step.last_outs
             with torch.no_grad():  # Model_._compute_loss_and_metrics (src/framework.py:152-156)
@@ -346,7 +376,8 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
                 for p in model.parameters():
                     opt.state[p]["momentum_buffer"] = step.momentum_buffer(p).detach().clone()
             if sched is not None and sched.device_run:
-                opt.param_groups[0]["lr"] = step.lr
+                for g, s in zip(opt.param_groups, lr_scales):
+                    g["lr"] = step.lr * s
             ck = {"model": model.state_dict(), "optimizer": opt.state_dict()}
             if sched is not None:
                 ck["lr_schedule"] = {"params": sched.params(), "step": int(step.sync_lr().step)}

@@ -248,7 +248,7 @@ typedef struct gm_tensor {
     long long n;
     long long offset;
     unsigned int group_mask;
-    unsigned int pad;
+    unsigned int pgroup;   /* parameter-group index: gm_group_sumsq_pg only (every other entry ignores it) */
 } gm_tensor;
 
 size_t gm_group_sumsq_scratch(long long total_elems);
@@ -425,6 +425,39 @@ int gm_group_sumsq_lr(const gm_tensor* table, float* const* mom, int ntensors, l
  * warmup_steps, n_milestones outside 0..GM_LR_MAX_MILESTONES, a negative or non-finite rate,
  * gamma or warmup_start, negative counts). */
 int gm_lr_at(const struct gm_lr_state* host_state, long long t, float* lr_out);
+
+/* ---------------------------------------------------------------------------
+ * Parameter groups and Nesterov momentum in the same pass: torch.optim.SGD with param groups that
+ * differ in learning rate and weight decay (dampening 0; momentum and nesterov per call).
+ * gm_tensor.pgroup is the tensor's index into a small caller-owned DEVICE table of (lr_scale,
+ * weight_decay) entries, read once per tensor segment (not a kernel argument: the host may rewrite
+ * an entry between replays of one captured step with a stream-ordered copy).  An index >=
+ * npgroups reads entry npgroups - 1.  The rate always comes from a device gm_lr_state (a caller
+ * without a schedule uses kind held).  A tensor in a group (s, wd) has the rate
+ * lr_g = (float)((double)lr->lr * (double)s) - the exact product, rounded once - and with
+ * g' = grad * grad_scale, each line one fused multiply-add:
+ *     d  = wd * w + g'
+ *     b' = momentum * b + d          (buffers given; else b' = d in registers)
+ *     u  = nesterov ? momentum * b' + d : b'
+ *     w' = w - lr_g * u
+ * Sums, skipped entries (grad NULL), buffers, scratch, gate and the finalize (sums, the gate's
+ * rule, then the state's advance) are gm_group_sumsq_lr's; mom != NULL iff momentum != 0;
+ * nesterov requires momentum > 0 (torch's rule).  One group (1, wd) without nesterov is
+ * gm_group_sumsq_lr(momentum, wd) bit for bit.
+ * ------------------------------------------------------------------------- */
+#define GM_SGD_MAX_PGROUPS 16
+struct gm_sgd_pgroup {
+    float lr_scale;
+    float weight_decay;
+};
+int gm_group_sumsq_pg(const gm_tensor* table, float* const* mom, int ntensors, long long total,
+                      int ngroups, float grad_scale, struct gm_lr_state* lr,
+                      const struct gm_sgd_pgroup* pgroups, int npgroups, float momentum, int nesterov,
+                      double* out, void* scratch, size_t scratch_bytes, void* gate, int gate_n,
+                      void* stream);
+/* Host only: checks a HOST copy of a group table - 1 <= npgroups <= GM_SGD_MAX_PGROUPS, every
+ * lr_scale and weight_decay finite and >= 0 (a device table cannot be checked at launch). */
+int gm_sgd_pgroups_check(const struct gm_sgd_pgroup* host_table, int npgroups);
 
 /* ---------------------------------------------------------------------------
  * ResNet trunk convolutions (torchvision resnet18/50 Conv2d, bias=False; called
