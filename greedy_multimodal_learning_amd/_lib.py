@@ -237,6 +237,37 @@ EXPORTS.update({
 })
 
 
+class ClipState(ctypes.Structure):
+    """gm_clip_state: the global-norm clip's device state (gm_group_sumsq_clip; max_norm at offset 0).
+    max_norm, eps and skip_nonfinite are the host's; the finalize launch of every pass writes the rest."""
+    _fields_ = [("max_norm", c_float), ("eps", c_float), ("skip_nonfinite", c_int), ("skipped_last", c_int),
+                ("total_sq", ctypes.c_double), ("coef", c_float), ("lr", c_float), ("steps", ctypes.c_longlong),
+                ("clipped", ctypes.c_longlong), ("skipped", ctypes.c_longlong)]
+
+
+EXPORTS.update({
+    "gm_group_sumsq_clip": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_float, c_void_p, c_void_p,
+                                    c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                    c_int, c_void_p]),
+    "gm_clip_state_check": (c_int, [c_void_p]),
+    "gm_clip_coef": (c_int, [ctypes.c_double, c_void_p, c_void_p]),
+})
+
+
+def clip_state_bytes(max_norm=float("inf"), eps=1e-6, skip_nonfinite=False):
+    """A fresh gm_clip_state (counters 0, coef 1) as bytes, after the library's host-side check."""
+    st = ClipState(max_norm=float(max_norm), eps=float(eps), skip_nonfinite=int(skip_nonfinite), coef=1.0)
+    check(load().gm_clip_state_check(ctypes.addressof(st)), "gm_clip_state_check")
+    return bytes(st)
+
+
+def clip_coef(total_sq, state):
+    """gm_clip_coef: the rule's coefficient for total_sq from a host ClipState's max_norm and eps."""
+    out = c_float()
+    check(load().gm_clip_coef(float(total_sq), ctypes.addressof(state), ctypes.addressof(out)), "gm_clip_coef")
+    return out.value
+
+
 class StemPack(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("dtype", c_int), ("N", c_int), ("C0", c_int), ("H", c_int), ("W", c_int),
                 ("pad", c_int), ("sn", ctypes.c_longlong), ("sc", ctypes.c_longlong), ("sh", ctypes.c_longlong),

@@ -128,6 +128,9 @@ class GroupNorms:
     `sums(..., lr_state=, pgroups=, nesterov=)` launches gm_group_sumsq_pg: each tensor's rate scale
     and weight decay from its entry of the device group table `pgroups`, by the index
     `pgroup_of(name)` written into the tensor table; optionally torch's Nesterov step.
+    `sums(..., lr_state=, clip_state=)` launches gm_group_sumsq_clip: any of the device-rate updates
+    above behind torch's clip_grad_norm_ and the non-finite step skip, decided on the device from a
+    gm_clip_state (three launches: sums, finalize, apply).
     """
 
     def __init__(self, named_params, branchnames, MMTMnames, pgroup_of=None):
@@ -191,7 +194,7 @@ class GroupNorms:
             self._out = torch.empty(2 * self.ngroups, dtype=torch.float64, device=self.device)
 
     def sums(self, grad_scale=1.0, lr=0.0, gate=None, gate_n=False, momentum=0.0, weight_decay=0.0,
-             momentum_buffers=None, lr_state=None, pgroups=None, nesterov=False):
+             momentum_buffers=None, lr_state=None, pgroups=None, nesterov=False, clip_state=None):
         """The step's group sums (and the fused SGD when lr != 0); gate (a device gm_gate_state /
         gm_gate_state_n tensor): the on-device gate's step runs in the same finalize launch.
         momentum / weight_decay (either non-zero: gm_group_sumsq_sgdm, whose update runs at
@@ -203,7 +206,11 @@ class GroupNorms:
         pgroups (a contiguous device fp32 tensor [npgroups, 2] of (lr_scale, weight_decay) rows, a
         gm_sgd_pgroup array; needs lr_state, and weight_decay must stay 0: the table owns it):
         gm_group_sumsq_pg, every tensor updated with its group's rate and decay; nesterov (with
-        pgroups and a momentum > 0): torch's Nesterov step."""
+        pgroups, or with clip_state alone, and a momentum > 0): torch's Nesterov step.
+        clip_state (a device uint8 tensor holding a gm_clip_state; needs lr_state; with or without
+        pgroups, nesterov, buffers and gate): gm_group_sumsq_clip - the gradient's global norm
+        clipped to the state's max_norm before the update, the update left out when the norm is not
+        finite and the state says so; the returned sums are those of the unclipped gradient."""
         L.load()
         if not self.params[0].is_cuda:
             raise L.GreedyMMLError("group norms run on HIP devices only (no CPU fallback)")
@@ -222,8 +229,15 @@ class GroupNorms:
                     or pgroups.dim() != 2 or pgroups.shape[1] != 2):
                 raise L.GreedyMMLError("group norms: pgroups must be a contiguous fp32 tensor [npgroups, 2] "
                                        "(lr_scale, weight_decay) on the parameters' device")
-        elif nesterov:
+        elif nesterov and clip_state is None:
             raise L.GreedyMMLError("group norms: nesterov needs a parameter-group table (pgroups)")
+        if clip_state is not None:
+            if lr_state is None:
+                raise L.GreedyMMLError("group norms: clip_state needs an lr_state (a held one without a schedule)")
+            if (clip_state.dtype != torch.uint8 or clip_state.device != self.device or not clip_state.is_contiguous()
+                    or clip_state.numel() < ctypes.sizeof(L.ClipState) or clip_state.data_ptr() % 8):
+                raise L.GreedyMMLError("group norms: clip_state must be a contiguous, 8-byte aligned uint8 tensor "
+                                       "holding a gm_clip_state on the parameters' device")
         self._build()
         out = torch.empty(2 * self.ngroups, dtype=torch.float64, device=self.device)
         sgdm = momentum != 0 or weight_decay != 0
@@ -234,7 +248,13 @@ class GroupNorms:
         lib, table, stream = L.load(), self._table.data_ptr(), L.stream_of(self.device)
         sizes = (len(self.params), self.total, self.ngroups, float(grad_scale), float(lr))
         bufs = (out.data_ptr(), self._scratch.data_ptr(), self._scratch.numel())
-        if pgroups is not None:
+        if clip_state is not None:
+            name = "gm_group_sumsq_clip"
+            rc = lib.gm_group_sumsq_clip(table, mom, *sizes[:4], lr_state.data_ptr(), L.ptr(pgroups),
+                                         0 if pgroups is None else pgroups.shape[0], float(momentum),
+                                         float(weight_decay), int(bool(nesterov)), clip_state.data_ptr(), *bufs,
+                                         L.ptr(gate), int(bool(gate_n)), stream)
+        elif pgroups is not None:
             name = "gm_group_sumsq_pg"
             rc = lib.gm_group_sumsq_pg(table, mom, *sizes[:4], lr_state.data_ptr(), pgroups.data_ptr(),
                                        pgroups.shape[0], float(momentum), int(bool(nesterov)), *bufs, L.ptr(gate),

@@ -21,9 +21,21 @@
 // finalize advances its schedule (lr_rule.h): one captured step for every rate.  The parameter-group
 // wrappers (k_group_sumsq_pg, gm_group_sumsq_pg) also read each tensor's rate scale and weight decay
 // from a small device table, per segment.
+//
+// The clipped forms (gm_group_sumsq_clip: torch's clip_grad_norm_ and the non-finite step skip, decided
+// on the device) need every gradient summed before any element is updated, so they split the pass
+// into three ordinary launches in stream (graph) order - nothing spins, nothing shares a launch:
+//   1. k_group_sumsq_tot[_runs]: the sums without an update (stream_segment<none, pass::sums>), with
+//      the total T = sum g'^2 over every entry as one more column behind the rows;
+//   2. k_group_finalize_clip: the group sums, then T -> coef, skipped_last (clip_rule.h), the gate's
+//      rule unless skipped, clip->lr = lrs->lr, the schedule's advance;
+//   3. k_group_apply[_pg]<upd>: the update alone (stream_segment<upd, pass::apply>) on
+//      g'' = (g * gscale) * coef at clip->lr, or nothing at all on skipped_last.
+// The same loops, update rule, argument functors and host path as the fused forms.
 #include <cmath>
 
 #include "gm_common.h"
+#include "clip_rule.h"
 #include "gate_rule.h"
 #include "lr_rule.h"
 
@@ -84,10 +96,20 @@ __device__ __forceinline__ float sgd_update(float w, float g, float& b, const sg
 // the gradient present below at compile time (inline it costs upd::mom 5 VGPRs and a wave per
 // SIMD).  mom also hands over a gradient without a buffer (the caller's error): nothing of it is
 // dereferenced or updated.
-template <upd U>
+// The clipped update (gm_group_sumsq_clip) splits the pass in two, the same loops both times:
+//   pass::sums  (upd::none) - the sums alone; mb is not read, but where the update form will
+//               stream it, it decides the 16-byte path as it does there, so the sums keep the
+//               fused pass's order bit for bit;
+//   pass::apply - the update alone with g'' = g' * coef (a second multiplication, not a folded
+//               scale); the sums are dead code, and an entry the fused pass would only sum is left.
+enum class pass { fused, sums, apply };
+
+template <upd U, pass P = pass::fused>
 __device__ __forceinline__ void stream_segment(const gm_tensor& T, float* __restrict__ mb, long long tb,
-                                               long long te, const sgdm_args& h, float& sw, float& sg) {
+                                               long long te, const sgdm_args& h, float& sw, float& sg,
+                                               float coef = 1.f) {
     constexpr bool MOM = has_buffer(U), EARLY = U == upd::decay || MOM;
+    if (P == pass::apply && (T.grad == nullptr || (MOM && mb == nullptr))) return;
     if (EARLY && (T.grad == nullptr || (MOM && mb == nullptr))) {
         stream_segment<upd::none>(T, nullptr, tb, te, h, sw, sg);
         return;
@@ -95,8 +117,9 @@ __device__ __forceinline__ void stream_segment(const gm_tensor& T, float* __rest
     float* __restrict__ p = T.param;
     const float* __restrict__ gr = T.grad;
     const bool hg = EARLY || gr != nullptr;
+    const bool bskew = MOM || (P == pass::sums && hg && mb != nullptr);
     const uintptr_t skew = (hg ? (uintptr_t)(p + tb) ^ (uintptr_t)(gr + tb) : (uintptr_t)0) |
-                           (MOM ? (uintptr_t)(p + tb) ^ (uintptr_t)(mb + tb) : (uintptr_t)0);
+                           (bskew ? (uintptr_t)(p + tb) ^ (uintptr_t)(mb + tb) : (uintptr_t)0);
     // scalar head up to 16-byte alignment of p (and g, mb)
     long long head = tb;
     if ((skew & 15) == 0) {
@@ -106,9 +129,10 @@ __device__ __forceinline__ void stream_segment(const gm_tensor& T, float* __rest
     }
     auto one = [&](long long i) {
         const float w = p[i];
-        const float g = hg ? gr[i] * h.gscale : 0.f;
+        float g = hg ? gr[i] * h.gscale : 0.f;
         sw = fmaf(w, w, sw);
         sg = fmaf(g, g, sg);
+        if (P == pass::apply) g *= coef;
         if (U != upd::none && hg) {
             float b = MOM ? mb[i] : 0.f;
             p[i] = sgd_update<U>(w, g, b, h);
@@ -126,6 +150,7 @@ __device__ __forceinline__ void stream_segment(const gm_tensor& T, float* __rest
         g.x *= h.gscale; g.y *= h.gscale; g.z *= h.gscale; g.w *= h.gscale;
         sg = fmaf(g.x, g.x, sg); sg = fmaf(g.y, g.y, sg);
         sg = fmaf(g.z, g.z, sg); sg = fmaf(g.w, g.w, sg);
+        if (P == pass::apply) { g.x *= coef; g.y *= coef; g.z *= coef; g.w *= coef; }
         if (U != upd::none)
             pv[i] = make_float4(sgd_update<U>(w.x, g.x, b.x, h), sgd_update<U>(w.y, g.y, b.y, h),
                                 sgd_update<U>(w.z, g.z, b.z, h), sgd_update<U>(w.w, g.w, b.w, h));
@@ -186,14 +211,18 @@ struct pgroup_args {
 
 // One workgroup's chunk, <= 8 groups: per-thread fp64 sums per group, folded over the waves in
 // fixed order into one row.  mom: the tensors' buffers (upd::mom and nest only)
-template <upd U, int MG, class H>
+// TOT (gm_group_sumsq_clip's sums launch, pass::sums): the chunk's g'^2 over every segment whatever
+// its mask, as one more fp64 sum folded the same way, written behind the row block:
+// rows[gridDim.x * 2 * ngroups + blockIdx.x].  The rows themselves are the same either way.
+template <upd U, int MG, class H, bool TOT = false>
 __device__ __forceinline__ void chunk_sums(const gm_tensor* __restrict__ tab, float* const* __restrict__ mom,
                                            int nt, long long total, int ngroups, const H& hs,
                                            long long chunk, double* __restrict__ rows) {
-    __shared__ double sred[4][2 * MG];
+    constexpr pass P = TOT ? pass::sums : pass::fused;
+    __shared__ double sred[4][2 * MG + (TOT ? 1 : 0)];
     const long long e0 = (long long)blockIdx.x * chunk;
     const long long e1 = min(total, e0 + chunk);
-    double gw[MG], gg[MG];
+    double gw[MG], gg[MG], tg = 0.0;
 #pragma unroll
     for (int g = 0; g < MG; ++g) { gw[g] = 0.0; gg[g] = 0.0; }
     int ti = find_tensor(tab, nt, e0);
@@ -203,11 +232,12 @@ __device__ __forceinline__ void chunk_sums(const gm_tensor* __restrict__ tab, fl
         const long long tb = e - T.offset;                       // first local element
         const long long te = min(T.n, e1 - T.offset);            // end (exclusive)
         float sw = 0.f, sg = 0.f;
-        stream_segment<U>(T, has_buffer(U) ? mom[ti] : nullptr, tb, te, hs(T), sw, sg);
+        stream_segment<U, P>(T, (has_buffer(U) || (TOT && mom)) ? mom[ti] : nullptr, tb, te, hs(T), sw, sg);
         const unsigned m = T.group_mask;
 #pragma unroll
         for (int g = 0; g < MG; ++g)
             if (g < ngroups && ((m >> g) & 1u)) { gw[g] += (double)sw; gg[g] += (double)sg; }
+        if (TOT) tg += (double)sg;
         e = T.offset + te;
         ++ti;
     }
@@ -219,10 +249,18 @@ __device__ __forceinline__ void chunk_sums(const gm_tensor* __restrict__ tab, fl
         const double s = wave_sum_d(gg[g]);
         if (lane == 0) { sred[wave][2 * g] = w; sred[wave][2 * g + 1] = s; }
     }
+    if (TOT) {
+        const double s = wave_sum_d(tg);
+        if (lane == 0) sred[wave][2 * MG] = s;
+    }
     __syncthreads();
     if (threadIdx.x < 2 * ngroups) {
         const int j = threadIdx.x;
         rows[(size_t)blockIdx.x * 2 * ngroups + j] = ((sred[0][j] + sred[1][j]) + sred[2][j]) + sred[3][j];
+    }
+    if (TOT && threadIdx.x == 64) {
+        const int j = 2 * MG;
+        rows[(size_t)gridDim.x * 2 * ngroups + blockIdx.x] = ((sred[0][j] + sred[1][j]) + sred[2][j]) + sred[3][j];
     }
 }
 
@@ -248,10 +286,12 @@ __device__ __forceinline__ void flush_run(double& aw, double& ag, unsigned mask,
     ag = 0.0;
 }
 
-template <upd U, class H>
+// TOT: as in chunk_sums - one more per-thread fp64 sum over the whole chunk, folded at the end
+template <upd U, class H, bool TOT = false>
 __device__ __forceinline__ void chunk_sums_runs(const gm_tensor* __restrict__ tab, float* const* __restrict__ mom,
                                                 int nt, long long total, int ngroups, const H& hs,
                                                 long long chunk, double* __restrict__ rows) {
+    constexpr pass P = TOT ? pass::sums : pass::fused;
     __shared__ double sred[4][2];
     __shared__ double acc[2 * kMaxGroups];
     if (threadIdx.x < 2 * kMaxGroups) acc[threadIdx.x] = 0.0;
@@ -259,7 +299,7 @@ __device__ __forceinline__ void chunk_sums_runs(const gm_tensor* __restrict__ ta
     const long long e1 = min(total, e0 + chunk);
     int ti = find_tensor(tab, nt, e0);
     unsigned cur = tab[ti].group_mask;
-    double aw = 0.0, ag = 0.0;
+    double aw = 0.0, ag = 0.0, tg = 0.0;
     long long e = e0;
     while (e < e1) {
         const gm_tensor T = tab[ti];
@@ -270,14 +310,43 @@ __device__ __forceinline__ void chunk_sums_runs(const gm_tensor* __restrict__ ta
         const long long tb = e - T.offset;
         const long long te = min(T.n, e1 - T.offset);
         float sw = 0.f, sg = 0.f;
-        stream_segment<U>(T, has_buffer(U) ? mom[ti] : nullptr, tb, te, hs(T), sw, sg);
+        stream_segment<U, P>(T, (has_buffer(U) || (TOT && mom)) ? mom[ti] : nullptr, tb, te, hs(T), sw, sg);
         aw += (double)sw;
         ag += (double)sg;
+        if (TOT) tg += (double)sg;
         e = T.offset + te;
         ++ti;
     }
     flush_run(aw, ag, cur, ngroups, sred, acc);
     if (threadIdx.x < 2 * ngroups) rows[(size_t)blockIdx.x * 2 * ngroups + threadIdx.x] = acc[threadIdx.x];
+    if (TOT) {  // (flush_run ended on a barrier: sred is free)
+        const double s = wave_sum_d(tg);
+        if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6][0] = s;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            rows[(size_t)gridDim.x * 2 * ngroups + blockIdx.x] = ((sred[0][0] + sred[1][0]) + sred[2][0]) + sred[3][0];
+    }
+}
+
+// The apply launch of gm_group_sumsq_clip: the same walk over the chunk's segments with the update
+// alone (pass::apply) - no sums, no rows, no finalize.  (Walking the chunks last to first, to start
+// with what the sums launch touched last, was measured and did not win: DESIGN §4.)
+template <upd U, class H>
+__device__ __forceinline__ void chunk_apply(const gm_tensor* __restrict__ tab, float* const* __restrict__ mom,
+                                            int nt, long long total, const H& hs, float coef, long long chunk) {
+    const long long e0 = (long long)blockIdx.x * chunk;
+    const long long e1 = min(total, e0 + chunk);
+    int ti = find_tensor(tab, nt, e0);
+    long long e = e0;
+    while (e < e1) {
+        const gm_tensor T = tab[ti];
+        const long long tb = e - T.offset;
+        const long long te = min(T.n, e1 - T.offset);
+        float sw = 0.f, sg = 0.f;  // (dead: the apply pass returns no sums)
+        stream_segment<U, pass::apply>(T, has_buffer(U) ? mom[ti] : nullptr, tb, te, hs(T), sw, sg, coef);
+        e = T.offset + te;
+        ++ti;
+    }
 }
 
 // The kernels: the two bodies above per update form.  The plain pair (gm_group_sumsq, _gate) keeps
@@ -359,6 +428,47 @@ __global__ __launch_bounds__(256) void k_group_sumsq_pg_runs(const gm_tensor* __
                        rows);
 }
 
+// The clipped forms (gm_group_sumsq_clip).  Launch 1, the sums with the total behind the rows
+// (mom: null, or the buffers the apply launch will stream - for the 16-byte path only):
+template <int MG>
+__global__ __launch_bounds__(256) void k_group_sumsq_tot(const gm_tensor* __restrict__ tab,
+                                                         float* const* __restrict__ mom, int nt, long long total,
+                                                         int ngroups, float gscale, long long chunk,
+                                                         double* __restrict__ rows) {
+    chunk_sums<upd::none, MG, uniform_args, true>(tab, mom, nt, total, ngroups, uniform_args{{gscale, 0.f, 0.f, 0.f}},
+                                                  chunk, rows);
+}
+
+__global__ __launch_bounds__(256) void k_group_sumsq_tot_runs(const gm_tensor* __restrict__ tab,
+                                                              float* const* __restrict__ mom, int nt,
+                                                              long long total, int ngroups, float gscale,
+                                                              long long chunk, double* __restrict__ rows) {
+    chunk_sums_runs<upd::none, uniform_args, true>(tab, mom, nt, total, ngroups, uniform_args{{gscale, 0.f, 0.f, 0.f}},
+                                                   chunk, rows);
+}
+
+// Launch 3, the apply: coefficient, rate and the skip decision are what the finalize launch left in
+// *clip, read once per workgroup (uniform loads that end in scalar registers, as lrs->lr does in the
+// device-rate forms).  A skipped step returns before it touches anything.
+template <upd U>
+__global__ __launch_bounds__(256) void k_group_apply(const gm_tensor* __restrict__ tab,
+                                                     float* const* __restrict__ mom, int nt, long long total,
+                                                     float gscale, const gm_clip_state* __restrict__ clip, float mu,
+                                                     float wd, long long chunk) {
+    if (clip->skipped_last) return;  // (uniform)
+    chunk_apply<U>(tab, mom, nt, total, uniform_args{{gscale, clip->lr, mu, wd}}, clip->coef, chunk);
+}
+
+template <upd U>
+__global__ __launch_bounds__(256) void k_group_apply_pg(const gm_tensor* __restrict__ tab,
+                                                        float* const* __restrict__ mom, int nt, long long total,
+                                                        float gscale, const gm_clip_state* __restrict__ clip,
+                                                        float mu, const gm_sgd_pgroup* __restrict__ pg, int npg,
+                                                        long long chunk) {
+    if (clip->skipped_last) return;  // (uniform)
+    chunk_apply<U>(tab, mom, nt, total, pgroup_args{gscale, clip->lr, mu, pg, (unsigned)(npg - 1)}, clip->coef, chunk);
+}
+
 // 1024 threads stream the [nrows][w] row block as one flat array with fully coalesced
 // 8-byte loads: thread t < S (S = the largest multiple of w <= 1024) owns column t % w and
 // reads elements t, t + S, ... (8 in flight).  The former form gave each thread whole
@@ -366,14 +476,12 @@ __global__ __launch_bounds__(256) void k_group_sumsq_pg_runs(const gm_tensor* __
 // the C2 step for 1451 rows).  Then per column 32 fixed partial sums of its slots and
 // their fixed-order total => deterministic.  (Threads t >= S hold 0 and take no part.)
 constexpr int kFinT = 1024;
-// gate (optional): the on-device gate's state - gm_gate_state (gate_n 0) or gm_gate_state_n (1) -
-// whose step rule thread 0 applies to the finished sums (gm_group_sumsq_gate: no gate launch)
-__device__ __forceinline__ void finalize_sums(const double* __restrict__ rows, int nrows, int ngroups,
-                                              double* __restrict__ out, void* gate, int gate_n) {
+// The column totals of a [nrows][w] block (w <= 2 kMaxGroups): to tot_s (shared, valid behind the
+// caller's next barrier) and, where given, to out.
+__device__ __forceinline__ void column_totals(const double* __restrict__ rows, int nrows, int w,
+                                              double* __restrict__ out, double* tot_s) {
     __shared__ double s[kFinT];
-    __shared__ double tot_s[2 * kMaxGroups];
     __shared__ double part[32 * 2 * kMaxGroups];
-    const int w = 2 * ngroups;
     const int S = (kFinT / w) * w, R = S / w;  // R row slots per column
     const int t = threadIdx.x;
     const long long n = (long long)nrows * w;
@@ -402,15 +510,25 @@ __device__ __forceinline__ void finalize_sums(const double* __restrict__ rows, i
     if (t < w) {
         double tot = 0.0;
         for (int q = 0; q < P; ++q) tot += part[q * w + t];
-        out[t] = tot;
+        if (out) out[t] = tot;
         tot_s[t] = tot;
     }
+}
+
+// gate (optional): the on-device gate's state - gm_gate_state (gate_n 0) or gm_gate_state_n (1) -
+// whose step rule thread 0 applies to the finished sums (gm_group_sumsq_gate: no gate launch)
+__device__ __forceinline__ void gate_rule(const double* tot_s, void* gate, int gate_n) {
+    if (gate_n) gate_strong_rule_n(tot_s, static_cast<gm_gate_state_n*>(gate));
+    else gate_strong_rule(tot_s, static_cast<gm_gate_state*>(gate));
+}
+
+__device__ __forceinline__ void finalize_sums(const double* __restrict__ rows, int nrows, int ngroups,
+                                              double* __restrict__ out, void* gate, int gate_n) {
+    __shared__ double tot_s[2 * kMaxGroups];
+    column_totals(rows, nrows, 2 * ngroups, out, tot_s);
     if (gate == nullptr) return;  // (uniform)
     __syncthreads();
-    if (t == 0) {
-        if (gate_n) gate_strong_rule_n(tot_s, static_cast<gm_gate_state_n*>(gate));
-        else gate_strong_rule(tot_s, static_cast<gm_gate_state*>(gate));
-    }
+    if (threadIdx.x == 0) gate_rule(tot_s, gate, gate_n);
 }
 
 __global__ __launch_bounds__(kFinT) void k_group_finalize(const double* __restrict__ rows, int nrows,
@@ -426,6 +544,28 @@ __global__ __launch_bounds__(kFinT) void k_group_finalize_lr(const double* __res
                                                              int gate_n, gm_lr_state* lrs) {
     finalize_sums(rows, nrows, ngroups, out, gate, gate_n);
     if (threadIdx.x == 0) lr_advance(lrs);
+}
+
+// The finalize of the clipped forms, between the sums launch and the apply launch: the group sums
+// as above (the same block, the same order), then the total from the column behind the rows, and
+// thread 0 runs the clip's rule, the gate's rule unless the step is skipped, hands the apply launch
+// its rate and advances the schedule - on a skipped step too (greedymml.h)
+__global__ __launch_bounds__(kFinT) void k_group_finalize_clip(const double* __restrict__ rows, int nrows,
+                                                               int ngroups, double* __restrict__ out, void* gate,
+                                                               int gate_n, gm_lr_state* lrs, gm_clip_state* clip) {
+    __shared__ double tot_s[2 * kMaxGroups];
+    __shared__ double tot_t[1];
+    column_totals(rows, nrows, 2 * ngroups, out, tot_s);
+    __syncthreads();  // (column_totals' LDS is read no more)
+    column_totals(rows + (size_t)nrows * 2 * ngroups, nrows, 1, nullptr, tot_t);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int skipped = clip_decide(tot_t[0], clip);
+        if (gate != nullptr && !skipped) gate_rule(tot_s, gate, gate_n);
+        clip->lr = lrs->lr;
+        lr_advance(lrs);
+        clip_count(clip);
+    }
 }
 
 }  // namespace gm
@@ -451,17 +591,28 @@ static auto pg_kernel(bool few) {
     return few ? k_group_sumsq_pg<U, 8> : k_group_sumsq_pg_runs<U>;
 }
 
+template <upd U>
+static void launch_apply(int nb, hipStream_t st, const gm_tensor* table, float* const* mom, int nt, long long total,
+                         const sgdm_args& h, const gm_clip_state* clip, const gm_sgd_pgroup* pg, int npg,
+                         long long chunk) {
+    if (pg) k_group_apply_pg<U><<<nb, 256, 0, st>>>(table, mom, nt, total, h.gscale, clip, h.mu, pg, npg, chunk);
+    else k_group_apply<U><<<nb, 256, 0, st>>>(table, mom, nt, total, h.gscale, clip, h.mu, h.wd, chunk);
+}
+
 // pg (with lrs): the device group table of gm_group_sumsq_pg (null: h.wd for every tensor)
+// clip (with lrs): gm_group_sumsq_clip - the sums launch, the clip's finalize, the apply launch
 static int group_sumsq(const gm_tensor* table, float* const* mom, int nt, long long total, int ngroups,
                        const sgdm_args& h, upd form, double* out, void* scratch, size_t scratch_bytes, void* gate,
                        int gate_n, void* stream, gm_lr_state* lrs = nullptr, const gm_sgd_pgroup* pg = nullptr,
-                       int npg = 0) {
+                       int npg = 0, gm_clip_state* clip = nullptr) {
     // (main, bypass) groups per branch: 4 for the two-branch gate, 2 nb for the N-branch one (nb in
     // the state: the rule reads 4 nb sums)
     GM_REQUIRE(!gate || (gate_n ? (ngroups >= 4 && ngroups % 2 == 0) : ngroups == 4),
                "group_sumsq_gate: %d groups do not match the %s gate", ngroups, gate_n ? "N-branch" : "two-branch");
     GM_REQUIRE(table && nt >= 1 && total >= 1, "group_sumsq: empty tensor table");
     GM_REQUIRE(ngroups >= 1 && ngroups <= kMaxGroups, "group_sumsq: ngroups must be 1..%d", kMaxGroups);
+    // (the total's column lies behind the rows in the scratch, which is sized for kMaxGroups)
+    GM_REQUIRE(!clip || ngroups < kMaxGroups, "group_sumsq_clip: ngroups must be 1..%d", kMaxGroups - 1);
     GM_REQUIRE(out, "group_sumsq: null output");
     const long long chunk = chunk_elems(total);
     GM_REQUIRE((total + chunk - 1) / chunk < (1ll << 31), "group_sumsq: too many elements");
@@ -472,6 +623,22 @@ static int group_sumsq(const gm_tensor* table, float* const* mom, int nt, long l
     double* rows = (double*)scratch;
     const bool few = ngroups <= 8;  // else the N-branch gates (C5: 12 branches -> 24 groups)
     const bool plain = form == upd::none || form == upd::sgd;
+    if (clip) {
+        const auto k = few ? k_group_sumsq_tot<8> : k_group_sumsq_tot_runs;
+        k<<<nb, 256, 0, st>>>(table, has_buffer(form) ? mom : nullptr, nt, total, ngroups, h.gscale, chunk, rows);
+        int rc = check_launch("k_group_sumsq_tot");
+        if (rc) return rc;
+        k_group_finalize_clip<<<1, kFinT, 0, st>>>(rows, nb, ngroups, out, gate, gate && gate_n ? 1 : 0, lrs, clip);
+        rc = check_launch("k_group_finalize_clip");
+        if (rc) return rc;
+        switch (form) {
+            case upd::nest: launch_apply<upd::nest>(nb, st, table, mom, nt, total, h, clip, pg, npg, chunk); break;
+            case upd::mom: launch_apply<upd::mom>(nb, st, table, mom, nt, total, h, clip, pg, npg, chunk); break;
+            case upd::decay: launch_apply<upd::decay>(nb, st, table, mom, nt, total, h, clip, pg, npg, chunk); break;
+            default: launch_apply<upd::sgd>(nb, st, table, mom, nt, total, h, clip, pg, npg, chunk); break;
+        }
+        return check_launch("k_group_apply");
+    }
     if (pg) {
         const auto k = form == upd::nest ? pg_kernel<upd::nest>(few)
                                          : (form == upd::mom ? pg_kernel<upd::mom>(few) : pg_kernel<upd::decay>(few));
@@ -555,6 +722,43 @@ extern "C" int gm_group_sumsq_pg(const gm_tensor* table, float* const* mom, int 
     const upd form = mom ? (nesterov ? upd::nest : upd::mom) : upd::decay;
     return group_sumsq(table, mom, nt, total, ngroups, {gscale, 0.f, momentum, 0.f}, form, out, scratch,
                        scratch_bytes, gate, gate_n, stream, lr, pgroups, npgroups);
+}
+
+extern "C" int gm_group_sumsq_clip(const gm_tensor* table, float* const* mom, int nt, long long total, int ngroups,
+                                   float gscale, gm_lr_state* lr, const gm_sgd_pgroup* pgroups, int npgroups,
+                                   float momentum, float weight_decay, int nesterov, gm_clip_state* clip,
+                                   double* out, void* scratch, size_t scratch_bytes, void* gate, int gate_n,
+                                   void* stream) {
+    GM_REQUIRE(clip, "group_sumsq_clip: null clip state");
+    GM_REQUIRE(lr, "group_sumsq_clip: null lr state");
+    GM_REQUIRE(!pgroups || (npgroups >= 1 && npgroups <= GM_SGD_MAX_PGROUPS),
+               "group_sumsq_clip: npgroups must be 1..%d", GM_SGD_MAX_PGROUPS);
+    GM_REQUIRE(std::isfinite(momentum) && momentum >= 0.f, "group_sumsq_clip: momentum must be finite and >= 0");
+    GM_REQUIRE(std::isfinite(weight_decay) && weight_decay >= 0.f,
+               "group_sumsq_clip: weight_decay must be finite and >= 0");
+    GM_REQUIRE(!pgroups || weight_decay == 0.f,
+               "group_sumsq_clip: the parameter-group table owns the weight decay (weight_decay must be 0)");
+    GM_REQUIRE(!nesterov || momentum > 0.f, "group_sumsq_clip: nesterov requires a momentum > 0");
+    GM_REQUIRE((mom != nullptr) == (momentum != 0.f),
+               "group_sumsq_clip: momentum buffers must be given if and only if momentum != 0");
+    const upd form = mom ? (nesterov ? upd::nest : upd::mom)
+                         : ((pgroups || weight_decay != 0.f) ? upd::decay : upd::sgd);
+    return group_sumsq(table, mom, nt, total, ngroups, {gscale, 0.f, momentum, weight_decay}, form, out, scratch,
+                       scratch_bytes, gate, gate_n, stream, lr, pgroups, pgroups ? npgroups : 0, clip);
+}
+
+extern "C" int gm_clip_state_check(const gm_clip_state* host) {
+    GM_REQUIRE(host, "clip_state_check: null state");
+    GM_REQUIRE(host->max_norm > 0.f, "clip_state_check: max_norm must be > 0 (+inf: never clips)");
+    GM_REQUIRE(std::isfinite(host->eps) && host->eps >= 0.f, "clip_state_check: eps must be finite and >= 0");
+    GM_REQUIRE(host->skip_nonfinite == 0 || host->skip_nonfinite == 1, "clip_state_check: skip_nonfinite must be 0 or 1");
+    return 0;
+}
+
+extern "C" int gm_clip_coef(double total_sq, const gm_clip_state* host, float* coef_out) {
+    GM_REQUIRE(host && coef_out, "clip_coef: null argument");
+    *coef_out = clip_coef(total_sq, host->max_norm, host->eps);
+    return 0;
 }
 
 extern "C" int gm_sgd_pgroups_check(const gm_sgd_pgroup* host, int npgroups) {

@@ -21,7 +21,10 @@ re-organised for the hardware:
   with `momentum` / `weight_decay` the same pass applies torch.optim.SGD's rule
   (`gm_group_sumsq_sgdm`) on a third flat buffer, the momentum buffers; with
   `param_groups` / `nesterov` (`gm_group_sumsq_pg`) each parameter's rate scale and
-  weight decay come from a small device table and the step may be Nesterov's;
+  weight decay come from a small device table and the step may be Nesterov's; with
+  `clip_grad_norm` / `skip_nonfinite_steps` (`gm_group_sumsq_clip`) the pass sums first,
+  decides torch's clip_grad_norm_ factor and the skip of a non-finite step on the device,
+  and applies the update in a second streaming launch;
 * the trunk runs in bf16 (autocast) on channels_last activations; master
   weights, gradients, the MMTM FC chain and all reductions stay fp32;
 * `graphs=True`: after one eager step, each curation setting
@@ -266,9 +269,20 @@ class BalancedStep:
                  process_group=None, bucket_mb=25.0, branchnames=("net_view_0", "net_view_1"),
                  MMTMnames=("visual", "skeleton"), graphs=False, device_gate=None, dp_buckets=None,
                  mmtm_excite=None, f32_contraction=None, momentum=0.0, weight_decay=0.0, lr_schedule=None,
-                 param_groups=None, nesterov=False):
+                 param_groups=None, nesterov=False, clip_grad_norm=None, skip_nonfinite_steps=False):
         import math
         self.model = model
+        # clip_grad_norm (torch's clip_grad_norm_ max_norm, > 0) / skip_nonfinite_steps (a step whose
+        # gradient's global norm is inf or NaN leaves parameters, momentum buffers and the gate alone):
+        # the update runs through gm_group_sumsq_clip, which decides both on the device from a small
+        # state (self.clip_state, made below, before any capture).  skip_nonfinite_steps alone is
+        # max_norm = +inf: the guard and the norm's log, no clipping.  Either implies a device rate, as
+        # the parameter groups do.  Both off (the default): nothing of this exists.
+        self.skip_nonfinite_steps = bool(skip_nonfinite_steps)
+        self._clip_max = None if clip_grad_norm is None else float(clip_grad_norm)
+        if self._clip_max is not None and not self._clip_max > 0.0:
+            raise ValueError(f"BalancedStep: clip_grad_norm must be > 0 (got {clip_grad_norm!r})")
+        clipping = self._clip_max is not None or self.skip_nonfinite_steps
         # param_groups (a param_groups.ParamGroups) / nesterov: the update runs through
         # gm_group_sumsq_pg - each parameter's rate scale and weight decay from a small device table
         # (self.pgroups, made below, before any capture), optionally torch's Nesterov step.  Either
@@ -277,7 +291,7 @@ class BalancedStep:
         self.param_groups, self.nesterov = param_groups, bool(nesterov)
         if self.nesterov and not float(momentum) > 0.0:
             raise ValueError("BalancedStep: nesterov=True requires a momentum > 0")
-        if (param_groups is not None or self.nesterov) and lr_schedule is None:
+        if (param_groups is not None or self.nesterov or clipping) and lr_schedule is None:
             from .lr_schedule import LRSchedule
             lr_schedule = LRSchedule("held", lr)
         # lr_schedule (an lr_schedule.LRSchedule; None: the rate is the `lr` argument of the update
@@ -341,6 +355,12 @@ class BalancedStep:
             self.norms = GroupNorms(named, list(branchnames), list(MMTMnames))
         if lr_schedule is not None:
             self.lr_state = torch.frombuffer(bytearray(lr_schedule.pack(0)), dtype=torch.uint8).to(self.device)
+        self.clip_state = None  # device uint8: a gm_clip_state
+        if clipping:
+            from ._lib import clip_state_bytes
+            raw = clip_state_bytes(math.inf if self._clip_max is None else self._clip_max, 1e-6,
+                                     self.skip_nonfinite_steps)  # (the library's host-side check)
+            self.clip_state = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
         # one flat zero momentum buffer at FlatParams' offsets (so co-aligned with the parameter
         # and gradient buffers: the fused pass keeps its 16-byte path), made here, before any
         # capture: the graph mutates it in place
@@ -499,6 +519,8 @@ class BalancedStep:
             kw = dict(momentum=self.momentum, weight_decay=self.weight_decay, momentum_buffers=self._mom_bufs)
         if self.device_gate:
             kw.update(gate=self.gate_state, gate_n=self.gate_n)
+        if self.clip_state is not None:  # gm_group_sumsq_clip: the same update behind the clip and the skip
+            kw.update(clip_state=self.clip_state)
         if self.lr_state is not None:  # gm_group_sumsq_lr: the rate is read from (and advanced in) device memory
             return self.norms.sums(grad_scale=1.0 / self.world, lr_state=self.lr_state, **kw)
         return self.norms.sums(grad_scale=1.0 / self.world, lr=self.lr, **kw)
@@ -550,6 +572,32 @@ class BalancedStep:
             st.lr = self._lr
         self.lr_state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8))
         self._lr_t = int(t)
+
+    # ---------------- gradient clipping ----------------
+    @property
+    def clip_grad_norm(self):
+        """The global-norm bound the next step clips to (None: no clipping)."""
+        return self._clip_max
+
+    @clip_grad_norm.setter
+    def clip_grad_norm(self, value):
+        if self.clip_state is None:
+            raise ValueError("BalancedStep.clip_grad_norm: the engine was made without clip_grad_norm / "
+                             "skip_nonfinite_steps (no clip state)")
+        import math
+        new = math.inf if value is None else float(value)
+        if not new > 0.0:
+            raise ValueError(f"BalancedStep.clip_grad_norm must be > 0 (got {value!r})")
+        # a stream-ordered fill of the state's first four bytes: no re-capture, one graph for every value
+        self.clip_state[:4].view(torch.float32).fill_(new)
+        self._clip_max = None if value is None else new
+
+    def sync_clip(self):
+        """The device gm_clip_state as its ctypes mirror (ClipState: total_sq, coef, skipped_last,
+        the counters, ...); one host sync, for tests and logs.  None without clipping."""
+        if self.clip_state is None:
+            return None
+        return L.ClipState.from_buffer_copy(self.clip_state.cpu().numpy().tobytes())
 
     def momentum_buffer(self, p):
         """The momentum buffer of parameter p: a view of the flat buffer shaped and strided like

@@ -185,7 +185,8 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
                   compute_dtype="fp32", graphs=True, f32_contraction="exact", eval_engine="modules",
                   eval_f32_trunk="modules", fused_momentum=False, lr_schedule=None, lr_warmup_steps=0,
                   lr_warmup_start=0.0, lr_milestones=(), lr_gamma=0.1, lr_total_steps=None, lr_min=0.0,
-                  param_groups=None, nesterov=False, optimizer_state_from=None):
+                  param_groups=None, nesterov=False, optimizer_state_from=None, clip_grad_norm=None,
+                  skip_nonfinite_steps=False):
     """Reference src/training_loop.py:86-143 + Model_.train_loop (src/framework.py:
     250-330) on the fused engine.  `optimizer` is the (lr, momentum, wd) triple of the
     reference's SGD (a torch SGD over the model's parameters holds the learning rate and
@@ -225,7 +226,14 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
     entry into `model`) - the momentum buffers continue; the gate's accumulators and curation state
     and the MMTM sites' running averages and step counters (plain attributes, not part of
     model.state_dict()) are NOT resumed.  All three follow fused_momentum's rule for a
-    non-zero momentum or weight decay."""
+    non-zero momentum or weight decay.
+    `clip_grad_norm` (None, or torch's clip_grad_norm_ max_norm > 0) and `skip_nonfinite_steps` (a
+    step whose gradient norm is inf or NaN updates nothing: parameters, momentum buffers and the
+    device gate stay as they were; the schedule still advances) are decided on the device inside the
+    step (BalancedStep(clip_grad_norm=, skip_nonfinite_steps=)); neither needs fused_momentum at
+    momentum = wd = 0.  With either on, each epoch's logs get the per-step lists `grad_norm` (before
+    clipping), `clip_coef` and `step_skipped`, and the printed line the epoch's clipped and skipped
+    steps.  A skipped step's loss is what it is: the NaN-loss stop works as without the option."""
     import math
 
     from .engine import BalancedStep
@@ -259,7 +267,8 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
     groups = from_config(param_groups, wd)
     step = BalancedStep(model, lr=lr, gate=gate, compute_dtype=cdt, channels_last=True, graphs=graphs,
                         f32_contraction=f32_contraction_arg(cdt, f32_contraction), momentum=momentum,
-                        weight_decay=wd, lr_schedule=sched, param_groups=groups, nesterov=nesterov)
+                        weight_decay=wd, lr_schedule=sched, param_groups=groups, nesterov=nesterov,
+                        clip_grad_norm=clip_grad_norm, skip_nonfinite_steps=skip_nonfinite_steps)
     # the reference's optimizer object (never stepped: the engine's fused pass applies the
     # update with the learning rate read from it)
     # (with parameter groups: the same groups - per-group lr, weight_decay, nesterov - so the
@@ -307,7 +316,7 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
         loss_sum = torch.zeros((), device=dev, dtype=torch.float64)
         acc_sum = torch.zeros((), device=dev, dtype=torch.float64)
         accm_sum = torch.zeros(nummodalities, device=dev, dtype=torch.float64)
-        idxs, d_bdr, cur, caring, snaps = [], [], [], [], []
+        idxs, d_bdr, cur, caring, snaps, clip_snaps = [], [], [], [], [], []
         for bi, (idx, x, y) in enumerate(train):
             if steps_per_epoch is not None and bi >= steps_per_epoch:
                 break
@@ -333,6 +342,8 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
                     d_bdr.append(float(getattr(gate, "d_BDR", 0.0) or 0.0))
                     cur.append(bool(step.flags.curation_mode))
                     caring.append(step.flags.caring_modality)
+            if step.clip_state is not None:
+                clip_snaps.append(step.clip_state.clone())
             if per_batch:
                 batch_logs = {"batch": bi + 1, "size": b, "loss": float(loss), "acc": float(a),
                               **{f"acc_modal_{i}": float(v) for i, v in enumerate(am)}}
@@ -355,6 +366,15 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
             logs.update({"d_BDR": d_bdr, "curation_mode": cur, "caring_modality": caring})
         if sched is not None:
             logs["lr"] = step.lr
+        n_clipped = n_skipped = 0
+        if step.clip_state is not None:  # decode the clip's per-step states (one copy)
+            cs = [L.ClipState.from_buffer_copy(raw.tobytes()) for raw in torch.stack(clip_snaps).cpu().numpy()] \
+                if clip_snaps else []
+            logs.update({"grad_norm": [math.sqrt(c.total_sq) if c.total_sq >= 0 else float("nan") for c in cs],
+                         "clip_coef": [float(c.coef) for c in cs],
+                         "step_skipped": [bool(c.skipped_last) for c in cs]})
+            n_skipped = sum(logs["step_skipped"])
+            n_clipped = sum(1 for c in cs if not c.skipped_last and c.coef < 1.0)
         # validation / test with the model's current curation flags (src/framework.py:146-148)
         if step.device_gate:
             step.sync_gate()
@@ -388,7 +408,8 @@ def training_loop(model, loss_function, metrics, optimizer, config, save_path, s
             torch.save(ck, os.path.join(save_path, "model_last_epoch.pt"))
         if verbose:
             print(f"epoch {epoch}: loss {logs['loss']:.4f} acc {logs['acc']:.2f} lr {step.lr:g}" +
-                  (f" val_acc {logs['val_acc']:.2f}" if "val_acc" in logs else ""), flush=True)
+                  (f" val_acc {logs['val_acc']:.2f}" if "val_acc" in logs else "") +
+                  (f" clipped {n_clipped} skipped {n_skipped}" if step.clip_state is not None else ""), flush=True)
         if flags.stop_training:
             break
     for c in others:

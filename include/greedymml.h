@@ -460,6 +460,73 @@ int gm_group_sumsq_pg(const gm_tensor* table, float* const* mom, int ntensors, l
 int gm_sgd_pgroups_check(const struct gm_sgd_pgroup* host_table, int npgroups);
 
 /* ---------------------------------------------------------------------------
+ * Global-norm gradient clipping and the non-finite step skip in the same pass:
+ * torch.nn.utils.clip_grad_norm_(max_norm, error_if_nonfinite=False) between backward and
+ * torch.optim.SGD.step, and a guard that leaves parameters and buffers alone when the gradient is
+ * not finite - both decided on the device, so a captured step (hipGraph) keeps no host sync.
+ * T is the sum of g'^2 = (grad * grad_scale)^2 in fp64 over every table entry exactly once (an
+ * entry without a gradient adds 0; the group masks play no part).  In fp64, rounded to fp32 once:
+ *     norm = sqrt(T)
+ *     c    = max_norm / (norm + eps)
+ *     coef = c > 1 ? 1 : c              (a NaN c stays NaN, as torch.clamp(max=1) keeps it)
+ * so max_norm = +inf gives coef == 1 for every finite T (guard and norm logging only), T = +inf
+ * gives 0 and T = NaN gives NaN.  The step is non-finite iff T is not finite.
+ * The clip factor depends on every gradient, so no element is updated before the last one is
+ * summed: three launches in stream (graph) order, none of which waits on another in-launch:
+ *   1. the sums: gm_group_sumsq's pass without an update (8 bytes per element), which also
+ *      carries T; the group sums are bit-identical to the other entry points';
+ *   2. the finalize (one workgroup): the group sums go to `out`; total_sq, coef and skipped_last =
+ *      skip_nonfinite && !isfinite(T) follow the rule; the gate's rule runs unless the step is
+ *      skipped (a skipped step did not happen: the gate's accumulators and window do not see
+ *      it); clip->lr = lr->lr, then the lr state advances; the counters;
+ *   3. the apply: a second streaming pass in the update form (12 bytes per element, 20 with
+ *      buffers) that reads clip->coef, clip->lr and clip->skipped_last once per workgroup.  On
+ *      skipped_last it returns at once: parameters and buffers stay bit for bit.  Otherwise per
+ *      element, two fp32 multiplications in this order (what a data-parallel mean followed by
+ *      clip_grad_norm_ rounds to), then gm_group_sumsq_pg's lines, each one fused multiply-add:
+ *          g'' = (grad * grad_scale) * coef
+ *          d   = wd * w + g''
+ *          b'  = momentum * b + d          (buffers given; else b' = d in registers)
+ *          u   = nesterov ? momentum * b' + d : b'
+ *          w'  = w - lr_g * u
+ * The schedule advances on a skipped step too: the pass count is what a host mirrors without a
+ * sync, and torch users step their scheduler after a skipped GradScaler step as well.  The sums
+ * and the gate always see the unclipped gradient.
+ * gm_clip_state is caller-owned DEVICE memory (56 B, 8-byte aligned); C callers name the type by
+ * its tag.  The host may rewrite max_norm between replays with a stream-ordered copy: it is
+ * neither a kernel argument nor part of a graph's key.
+ * ------------------------------------------------------------------------- */
+struct gm_clip_state {
+    float max_norm;           /* offset 0, host-set: > 0, +inf allowed (never clips) */
+    float eps;                /* host-set: finite, >= 0 (torch: 1e-6) */
+    int skip_nonfinite;       /* host-set: 0 or 1 */
+    int skipped_last;         /* the rest is written by the finalize launch of every pass: 0 or 1 */
+    double total_sq;          /* T */
+    float coef;
+    float lr;                 /* the rate this pass's apply launch uses (lr->lr before its advance) */
+    long long steps;          /* passes */
+    long long clipped;        /* passes that ran with coef < 1 */
+    long long skipped;        /* passes skipped */
+};
+/* One entry for every update form: pgroups != NULL is gm_group_sumsq_pg's update (npgroups as
+ * there; weight_decay must be 0, the table owns it), pgroups == NULL gm_group_sumsq_lr's with
+ * weight_decay for every tensor (npgroups ignored); nesterov works with either.  The other
+ * arguments and their rules are gm_group_sumsq_pg's; lr and clip must not be NULL.  T travels in
+ * the scratch beside the group rows, which leaves room for ngroups <= 31: more is refused before
+ * any launch.  gm_group_sumsq_scratch is unchanged. */
+int gm_group_sumsq_clip(const gm_tensor* table, float* const* mom, int ntensors, long long total,
+                        int ngroups, float grad_scale, struct gm_lr_state* lr,
+                        const struct gm_sgd_pgroup* pgroups, int npgroups, float momentum,
+                        float weight_decay, int nesterov, struct gm_clip_state* clip, double* out,
+                        void* scratch, size_t scratch_bytes, void* gate, int gate_n, void* stream);
+/* Host only: checks the host-set fields of a HOST copy - max_norm > 0 (NaN refused, +inf
+ * allowed), eps finite and >= 0, skip_nonfinite 0 or 1 (a device state cannot be checked at
+ * launch). */
+int gm_clip_state_check(const struct gm_clip_state* host_state);
+/* Host only: coef of the rule above for total_sq, from a HOST copy's max_norm and eps. */
+int gm_clip_coef(double total_sq, const struct gm_clip_state* host_state, float* coef_out);
+
+/* ---------------------------------------------------------------------------
  * ResNet trunk convolutions (torchvision resnet18/50 Conv2d, bias=False; called
  * piecewise at reference src/model.py:65-106) as bf16 implicit GEMMs on MFMA.
  * Activations NHWC [N][H][W][C] bf16, weights KRSC [K][R][S][C] bf16 (PyTorch

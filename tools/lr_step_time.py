@@ -8,7 +8,12 @@ Then one change of the rate on each engine and the wall time of the first step a
 drained before and after): the default engine synchronises, destroys its graphs and captures a new
 one; the held device state is a 4-byte fill in front of the same replay.  One JSON line.
 
-    python tools/lr_step_time.py [--rounds 7] [--steps 20] [--out FILE]
+    python tools/lr_step_time.py [--rounds 7] [--steps 20] [--clip] [--out FILE]
+
+--clip adds a third engine on the same seed, alternating with the other two: the held device rate
+plus BalancedStep(clip_grad_norm=1e9, skip_nonfinite_steps=True) - a bound that never clips, so it
+computes what the others compute with gm_group_sumsq_clip's three launches in place of two
+(`clip_minus_default_ms`, `clip_minus_held_ms`: differences of medians, against the spreads).
 """
 import argparse
 import json
@@ -24,6 +29,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--clip", action="store_true", help="a third engine with the clip on at a bound that never clips")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -39,13 +45,16 @@ def main():
     xs = [torch.randn(2, B, 224, 224, 3, device=dev, generator=g).bfloat16().permute(1, 0, 4, 2, 3) for _ in range(2)]
     ys = [torch.randint(0, 40, (B,), device=dev, generator=g) for _ in range(2)]
     eng = {}
-    for name, sch in (("default", None), ("held_device_lr", LRSchedule("held", LR))):
+    configs = [("default", None, {}), ("held_device_lr", LRSchedule("held", LR), {})]
+    if a.clip:
+        configs.append(("clip_never_clips", LRSchedule("held", LR), dict(clip_grad_norm=1e9, skip_nonfinite_steps=True)))
+    for name, sch, extra in configs:
         torch.manual_seed(0)
         model = MMTM_MVCNN().to(dev)
         gate = Bias_Mitigation_Strong(epsilon=0.01, curation_windowsize=5, branchnames=["net_view_0", "net_view_1"],
                                       starting_epoch=1, MMTMnames=["visual", "skeleton"])
         st = BalancedStep(model, lr=LR, gate=gate, compute_dtype=torch.bfloat16, channels_last=True, graphs=True,
-                          lr_schedule=sch)
+                          lr_schedule=sch, **extra)
         st.on_epoch_begin(1)
         st.bind_batches(*zip(xs, ys))
         for i in range(WARM):
@@ -71,6 +80,11 @@ def main():
         res[name] = {"step_ms": round(statistics.median(ms[name]), 4),
                      "spread_ms": round(max(ms[name]) - min(ms[name]), 4), "graphs": len(eng[name]._graphs)}
     res["held_minus_default_ms"] = round(res["held_device_lr"]["step_ms"] - res["default"]["step_ms"], 4)
+    if a.clip:
+        res["clip_minus_default_ms"] = round(res["clip_never_clips"]["step_ms"] - res["default"]["step_ms"], 4)
+        res["clip_minus_held_ms"] = round(res["clip_never_clips"]["step_ms"] - res["held_device_lr"]["step_ms"], 4)
+        c = eng["clip_never_clips"].sync_clip()
+        res["clip_never_clips"].update(steps=c.steps, clipped=c.clipped, skipped=c.skipped, grad_norm=c.total_sq ** 0.5)
     # one change of the rate: the first step after it on each slot's graph, then a settled step
     for name, st in eng.items():
         st.lr = 0.03
@@ -79,8 +93,8 @@ def main():
         res[name]["settled_step_ms"] = round(timed(st, a.steps), 4)
         res[name]["graphs_after"] = len(st._graphs)
         assert st.graphs, st.capture_failures
-    same = all(torch.equal(p, q) for p, q in zip(eng["default"].model.state_dict().values(),
-                                                 eng["held_device_lr"].model.state_dict().values()))
+    same = all(torch.equal(p, q) for name in list(eng)[1:]
+               for p, q in zip(eng["default"].model.state_dict().values(), eng[name].model.state_dict().values()))
     res["engines_bit_identical"] = bool(same)
     line = json.dumps(res)
     print(line)
