@@ -1,6 +1,6 @@
 // The global-norm gradient clip's rule (gm_clip_state, greedymml.h) as one function of the step's
 // total sum of squares, shared by the host (gm_clip_coef) and the device: thread 0 of
-// k_group_finalize_clip (group_sumsq.hip) evaluates it between the sums launch and the apply launch
+// k_group_finalize (group_sumsq.hip) evaluates it between the sums launch and the apply launch
 // of gm_group_sumsq_clip.  torch.nn.utils.clip_grad_norm_(error_if_nonfinite=False): fp64
 // throughout, one rounding to fp32.
 #pragma once
@@ -22,7 +22,7 @@ __host__ __device__ inline float clip_coef(double total_sq, float max_norm, floa
 __host__ __device__ inline bool clip_nonfinite(double total_sq) { return !(fabs(total_sq) <= 1.7976931348623157e308); }
 
 // One pass's finalize, in two parts around the gate's rule and the rate's hand-over
-// (k_group_finalize_clip).  One thread, plain stores.
+// (k_group_finalize).  One thread, plain stores.
 // First: total, coefficient and the skip decision.  Returns skipped_last (the caller leaves the
 // gate's rule out of a skipped step).
 __device__ inline int clip_decide(double total_sq, gm_clip_state* st) {

@@ -13,25 +13,27 @@
 // + read and write b).  Deterministic.
 //
 // One of each: the update rule (sgd_update<upd>), the streaming loops and sums
-// (stream_segment<upd>), the chunk body per group-count form (chunk_sums, chunk_sums_runs) and
-// the host launch path (group_sumsq).  The update form - none, sgd, decay, mom, nest - is a template
-// parameter all the way down; the __global__ kernels and the entry points are wrappers that
-// choose it.  The device-rate wrappers (k_group_sumsq_dlr, gm_group_sumsq_lr) read
-// the learning rate from a gm_lr_state in device memory instead of an argument, and their
-// finalize advances its schedule (lr_rule.h): one captured step for every rate.  The parameter-group
-// wrappers (k_group_sumsq_pg, gm_group_sumsq_pg) also read each tensor's rate scale and weight decay
-// from a small device table, per segment.
+// (stream_segment<upd>), the chunk body per group-count form (chunk_sums, chunk_sums_runs), the
+// argument rules of the entry points (check_update) and the host launch path (group_sumsq).  The
+// update form - none, sgd, decay, mom, nest - is a template parameter all the way down.
 //
-// The clipped forms (gm_group_sumsq_clip: torch's clip_grad_norm_ and the non-finite step skip, decided
-// on the device) need every gradient summed before any element is updated, so they split the pass
-// into three ordinary launches in stream (graph) order - nothing spins, nothing shares a launch:
-//   1. k_group_sumsq_tot[_runs]: the sums without an update (stream_segment<none, pass::sums>), with
-//      the total T = sum g'^2 over every entry as one more column behind the rows;
-//   2. k_group_finalize_clip: the group sums, then T -> coef, skipped_last (clip_rule.h), the gate's
-//      rule unless skipped, clip->lr = lrs->lr, the schedule's advance;
-//   3. k_group_apply[_pg]<upd>: the update alone (stream_segment<upd, pass::apply>) on
-//      g'' = (g * gscale) * coef at clip->lr, or nothing at all on skipped_last.
-// The same loops, update rule, argument functors and host path as the fused forms.
+// Three __global__ templates; the two streaming ones take one by-value pass_args and the four
+// arrays they stream through:
+//   k_group_sumsq<upd, body, H, TOT>  the sums, fused with the update unless upd::none.  body: the
+//       <= 8-group form or the run form.  H: where a segment's hyper-parameters come from -
+//       uniform_args (one set for the pass) or pgroup_args (gm_group_sumsq_pg: each tensor's rate
+//       scale and weight decay from a small device table).  The rate is the argument, or, given a
+//       gm_lr_state (gm_group_sumsq_lr, _pg), its lr in device memory: one captured step for every
+//       rate.  TOT: the total T = sum g'^2 over every entry as one more column behind the rows.
+//   k_group_finalize  one block: the rows' column totals in fixed order, then thread 0 applies what
+//       the entry asked for - the clip's rule, the gate's rule, the schedule's advance (lr_rule.h).
+//   k_group_apply<upd, H>  the update alone (stream_segment<upd, pass::apply>).
+// Every entry but one is k_group_sumsq then k_group_finalize.  The clipped entry
+// (gm_group_sumsq_clip: torch's clip_grad_norm_ and the non-finite step skip, decided on the
+// device) needs every gradient summed before any element is updated, so it is three ordinary
+// launches in stream (graph) order - nothing spins, nothing shares a launch: the sums without an
+// update (k_group_sumsq<none, ., uniform_args, TOT>), the finalize, and k_group_apply on
+// g'' = (g * gscale) * coef at clip->lr, or nothing at all on skipped_last.
 #include <cmath>
 
 #include "gm_common.h"
@@ -185,11 +187,31 @@ __device__ __forceinline__ void stream_segment(const gm_tensor& T, float* __rest
     for (long long i = head + nv * 4 + threadIdx.x; i < te; i += 256) one(i);
 }
 
+// What the two streaming kernels take: one by-value pass_args, and beside it the four arrays the
+// loops read and write through - the tensor table, the tensors' momentum buffers (null without),
+// the parameter-group table (pgroup_args only) and the workgroups' rows (k_group_sumsq only) - each
+// a __restrict__ kernel parameter of its own.  Only there does __restrict__ reach the compiler:
+// with the four pointers inside the struct upd::mom takes up to 6 more VGPRs and loses its fourth
+// wave per SIMD in three instantiations.  A kernel loads only the fields it reads.
+struct pass_args {
+    int nt;
+    long long total;
+    int ngroups;  // k_group_sumsq only
+    float gscale, lr, mu, wd;
+    const gm_lr_state* lrs;  // k_group_sumsq: non-null: the rate is lrs->lr, not lr
+    int npg;                 // pgroup_args only
+    const gm_clip_state* clip;  // k_group_apply only
+    long long chunk;
+};
+
 // The hyper-parameters of a tensor segment, as the chunk bodies below ask for them (hs(T)): one
 // sgdm_args for the whole pass, or per parameter group.  A segment is uniform across the workgroup,
-// so either way they sit in scalar registers.
+// so either way they sit in scalar registers.  The choice is a compile-time one: a run-time "table
+// or no table" test in one functor costs upd::mom its fourth wave per SIMD.
 struct uniform_args {
     sgdm_args h;
+    __device__ __forceinline__ uniform_args(const pass_args& a, const gm_sgd_pgroup*, float lr)
+        : h{a.gscale, lr, a.mu, a.wd} {}
     __device__ __forceinline__ const sgdm_args& operator()(const gm_tensor&) const { return h; }
 };
 
@@ -199,6 +221,8 @@ struct pgroup_args {
     float gscale, lr, mu;
     const gm_sgd_pgroup* __restrict__ pg;
     unsigned last;  // npgroups - 1
+    __device__ __forceinline__ pgroup_args(const pass_args& a, const gm_sgd_pgroup* pg, float lr)
+        : gscale(a.gscale), lr(lr), mu(a.mu), pg(pg), last((unsigned)(a.npg - 1)) {}
     __device__ __forceinline__ sgdm_args operator()(const gm_tensor& T) const {
         const gm_sgd_pgroup e = pg[min(T.pgroup, last)];
         // (the fp64 product is vector arithmetic; readfirstlane puts the uniform result back into a
@@ -349,124 +373,30 @@ __device__ __forceinline__ void chunk_apply(const gm_tensor* __restrict__ tab, f
     }
 }
 
-// The kernels: the two bodies above per update form.  The plain pair (gm_group_sumsq, _gate) keeps
-// its name and argument layout: profiles and tools find the step boundary by `k_group_sumsq<true`.
-template <bool SGD, int MG>
-__global__ __launch_bounds__(256) void k_group_sumsq(const gm_tensor* __restrict__ tab, int nt,
-                                                     long long total, int ngroups, float gscale,
-                                                     float lr, long long chunk, double* __restrict__ rows) {
-    chunk_sums<SGD ? upd::sgd : upd::none, MG>(tab, nullptr, nt, total, ngroups, uniform_args{{gscale, lr, 0.f, 0.f}},
-                                               chunk, rows);
+// The sums, fused with the update of form U: one chunk body with one functor.  The rate is read
+// once per workgroup - the argument, or *lrs (a uniform load that ends in a scalar register as the
+// argument does).  TOT (gm_group_sumsq_clip's sums launch, U none): mom is null, or the buffers
+// the apply launch will stream - for the 16-byte path only.
+enum class body { few, runs };
+
+template <upd U, body B, class H, bool TOT>
+__global__ __launch_bounds__(256) void k_group_sumsq(pass_args a, const gm_tensor* __restrict__ tab,
+                                                     float* const* __restrict__ mom, const gm_sgd_pgroup* __restrict__ pg,
+                                                     double* __restrict__ rows) {
+    const H hs(a, pg, a.lrs ? a.lrs->lr : a.lr);
+    if constexpr (B == body::few) chunk_sums<U, 8, H, TOT>(tab, mom, a.nt, a.total, a.ngroups, hs, a.chunk, rows);
+    else chunk_sums_runs<U, H, TOT>(tab, mom, a.nt, a.total, a.ngroups, hs, a.chunk, rows);
 }
 
-template <bool SGD>
-__global__ __launch_bounds__(256) void k_group_sumsq_runs(const gm_tensor* __restrict__ tab, int nt,
-                                                          long long total, int ngroups, float gscale,
-                                                          float lr, long long chunk, double* __restrict__ rows) {
-    chunk_sums_runs<SGD ? upd::sgd : upd::none>(tab, nullptr, nt, total, ngroups, uniform_args{{gscale, lr, 0.f, 0.f}},
-                                                chunk, rows);
-}
-
-template <bool MOM, int MG>
-__global__ __launch_bounds__(256) void k_group_sumsq_sgdm(const gm_tensor* __restrict__ tab,
-                                                          float* const* __restrict__ mom, int nt, long long total,
-                                                          int ngroups, sgdm_args h, long long chunk,
-                                                          double* __restrict__ rows) {
-    chunk_sums<MOM ? upd::mom : upd::decay, MG>(tab, mom, nt, total, ngroups, uniform_args{h}, chunk, rows);
-}
-
-template <bool MOM>
-__global__ __launch_bounds__(256) void k_group_sumsq_sgdm_runs(const gm_tensor* __restrict__ tab,
-                                                               float* const* __restrict__ mom, int nt,
-                                                               long long total, int ngroups, sgdm_args h,
-                                                               long long chunk, double* __restrict__ rows) {
-    chunk_sums_runs<MOM ? upd::mom : upd::decay>(tab, mom, nt, total, ngroups, uniform_args{h}, chunk, rows);
-}
-
-// The device-rate forms: the rate is *lrs, read once per workgroup (a uniform load that ends in a
-// scalar register as the argument does); otherwise the kernels above, for every update form.
-template <upd U, int MG>
-__global__ __launch_bounds__(256) void k_group_sumsq_dlr(const gm_tensor* __restrict__ tab,
-                                                         float* const* __restrict__ mom, int nt, long long total,
-                                                         int ngroups, float gscale,
-                                                         const gm_lr_state* __restrict__ lrs, float mu, float wd,
-                                                         long long chunk, double* __restrict__ rows) {
-    chunk_sums<U, MG>(tab, mom, nt, total, ngroups, uniform_args{{gscale, lrs->lr, mu, wd}}, chunk, rows);
-}
-
-template <upd U>
-__global__ __launch_bounds__(256) void k_group_sumsq_dlr_runs(const gm_tensor* __restrict__ tab,
-                                                              float* const* __restrict__ mom, int nt,
-                                                              long long total, int ngroups, float gscale,
-                                                              const gm_lr_state* __restrict__ lrs, float mu,
-                                                              float wd, long long chunk,
-                                                              double* __restrict__ rows) {
-    chunk_sums_runs<U>(tab, mom, nt, total, ngroups, uniform_args{{gscale, lrs->lr, mu, wd}}, chunk, rows);
-}
-
-// The parameter-group forms (decay, mom, nest): the device-rate kernels with each segment's rate
-// scale and weight decay read from the group table pg[0..npg) by the tensor's index (pgroup_args).
-template <upd U, int MG>
-__global__ __launch_bounds__(256) void k_group_sumsq_pg(const gm_tensor* __restrict__ tab,
-                                                        float* const* __restrict__ mom, int nt, long long total,
-                                                        int ngroups, float gscale,
-                                                        const gm_lr_state* __restrict__ lrs, float mu,
-                                                        const gm_sgd_pgroup* __restrict__ pg, int npg,
-                                                        long long chunk, double* __restrict__ rows) {
-    chunk_sums<U, MG>(tab, mom, nt, total, ngroups, pgroup_args{gscale, lrs->lr, mu, pg, (unsigned)(npg - 1)}, chunk,
-                      rows);
-}
-
-template <upd U>
-__global__ __launch_bounds__(256) void k_group_sumsq_pg_runs(const gm_tensor* __restrict__ tab,
-                                                             float* const* __restrict__ mom, int nt,
-                                                             long long total, int ngroups, float gscale,
-                                                             const gm_lr_state* __restrict__ lrs, float mu,
-                                                             const gm_sgd_pgroup* __restrict__ pg, int npg,
-                                                             long long chunk, double* __restrict__ rows) {
-    chunk_sums_runs<U>(tab, mom, nt, total, ngroups, pgroup_args{gscale, lrs->lr, mu, pg, (unsigned)(npg - 1)}, chunk,
-                       rows);
-}
-
-// The clipped forms (gm_group_sumsq_clip).  Launch 1, the sums with the total behind the rows
-// (mom: null, or the buffers the apply launch will stream - for the 16-byte path only):
-template <int MG>
-__global__ __launch_bounds__(256) void k_group_sumsq_tot(const gm_tensor* __restrict__ tab,
-                                                         float* const* __restrict__ mom, int nt, long long total,
-                                                         int ngroups, float gscale, long long chunk,
-                                                         double* __restrict__ rows) {
-    chunk_sums<upd::none, MG, uniform_args, true>(tab, mom, nt, total, ngroups, uniform_args{{gscale, 0.f, 0.f, 0.f}},
-                                                  chunk, rows);
-}
-
-__global__ __launch_bounds__(256) void k_group_sumsq_tot_runs(const gm_tensor* __restrict__ tab,
-                                                              float* const* __restrict__ mom, int nt,
-                                                              long long total, int ngroups, float gscale,
-                                                              long long chunk, double* __restrict__ rows) {
-    chunk_sums_runs<upd::none, uniform_args, true>(tab, mom, nt, total, ngroups, uniform_args{{gscale, 0.f, 0.f, 0.f}},
-                                                   chunk, rows);
-}
-
-// Launch 3, the apply: coefficient, rate and the skip decision are what the finalize launch left in
-// *clip, read once per workgroup (uniform loads that end in scalar registers, as lrs->lr does in the
-// device-rate forms).  A skipped step returns before it touches anything.
-template <upd U>
-__global__ __launch_bounds__(256) void k_group_apply(const gm_tensor* __restrict__ tab,
-                                                     float* const* __restrict__ mom, int nt, long long total,
-                                                     float gscale, const gm_clip_state* __restrict__ clip, float mu,
-                                                     float wd, long long chunk) {
-    if (clip->skipped_last) return;  // (uniform)
-    chunk_apply<U>(tab, mom, nt, total, uniform_args{{gscale, clip->lr, mu, wd}}, clip->coef, chunk);
-}
-
-template <upd U>
-__global__ __launch_bounds__(256) void k_group_apply_pg(const gm_tensor* __restrict__ tab,
-                                                        float* const* __restrict__ mom, int nt, long long total,
-                                                        float gscale, const gm_clip_state* __restrict__ clip,
-                                                        float mu, const gm_sgd_pgroup* __restrict__ pg, int npg,
-                                                        long long chunk) {
-    if (clip->skipped_last) return;  // (uniform)
-    chunk_apply<U>(tab, mom, nt, total, pgroup_args{gscale, clip->lr, mu, pg, (unsigned)(npg - 1)}, clip->coef, chunk);
+// The apply launch of gm_group_sumsq_clip: coefficient, rate and the skip decision are what the
+// finalize launch left in *clip, read once per workgroup (uniform loads, as lrs->lr above).  A
+// skipped step returns before it touches anything.  (rows: unused - one signature for both.)
+template <upd U, class H>
+__global__ __launch_bounds__(256) void k_group_apply(pass_args a, const gm_tensor* __restrict__ tab,
+                                                     float* const* __restrict__ mom, const gm_sgd_pgroup* __restrict__ pg,
+                                                     double* __restrict__ rows) {
+    if (a.clip->skipped_last) return;  // (uniform)
+    chunk_apply<U>(tab, mom, a.nt, a.total, H(a, pg, a.clip->lr), a.clip->coef, a.chunk);
 }
 
 // 1024 threads stream the [nrows][w] row block as one flat array with fully coalesced
@@ -522,49 +452,31 @@ __device__ __forceinline__ void gate_rule(const double* tot_s, void* gate, int g
     else gate_strong_rule(tot_s, static_cast<gm_gate_state*>(gate));
 }
 
-__device__ __forceinline__ void finalize_sums(const double* __restrict__ rows, int nrows, int ngroups,
-                                              double* __restrict__ out, void* gate, int gate_n) {
-    __shared__ double tot_s[2 * kMaxGroups];
-    column_totals(rows, nrows, 2 * ngroups, out, tot_s);
-    if (gate == nullptr) return;  // (uniform)
-    __syncthreads();
-    if (threadIdx.x == 0) gate_rule(tot_s, gate, gate_n);
-}
-
+// The finalize of every entry: the group sums, then what thread 0 owes the state the entry gave -
+//   gate  the gate's rule on the finished sums (not on a skipped step);
+//   lrs   the schedule's advance, after the sums and the gate's rule (the pass that read the old
+//         rate ended before this launch began);
+//   clip  (with lrs; between the sums launch and the apply launch) first of all the clip's rule
+//         on the total from the column behind the rows, and the rate handed to the apply launch
+//         before the schedule advances - which it does on a skipped step too (greedymml.h).
 __global__ __launch_bounds__(kFinT) void k_group_finalize(const double* __restrict__ rows, int nrows,
-                                                          int ngroups, double* __restrict__ out,
-                                                          void* gate = nullptr, int gate_n = 0) {
-    finalize_sums(rows, nrows, ngroups, out, gate, gate_n);
-}
-
-// The finalize of the device-rate forms: thread 0 also advances the rate's schedule, after the
-// sums and the gate's rule (the pass that read the old rate ended before this launch began)
-__global__ __launch_bounds__(kFinT) void k_group_finalize_lr(const double* __restrict__ rows, int nrows,
-                                                             int ngroups, double* __restrict__ out, void* gate,
-                                                             int gate_n, gm_lr_state* lrs) {
-    finalize_sums(rows, nrows, ngroups, out, gate, gate_n);
-    if (threadIdx.x == 0) lr_advance(lrs);
-}
-
-// The finalize of the clipped forms, between the sums launch and the apply launch: the group sums
-// as above (the same block, the same order), then the total from the column behind the rows, and
-// thread 0 runs the clip's rule, the gate's rule unless the step is skipped, hands the apply launch
-// its rate and advances the schedule - on a skipped step too (greedymml.h)
-__global__ __launch_bounds__(kFinT) void k_group_finalize_clip(const double* __restrict__ rows, int nrows,
-                                                               int ngroups, double* __restrict__ out, void* gate,
-                                                               int gate_n, gm_lr_state* lrs, gm_clip_state* clip) {
+                                                          int ngroups, double* __restrict__ out, void* gate,
+                                                          int gate_n, gm_lr_state* lrs, gm_clip_state* clip) {
     __shared__ double tot_s[2 * kMaxGroups];
     __shared__ double tot_t[1];
     column_totals(rows, nrows, 2 * ngroups, out, tot_s);
-    __syncthreads();  // (column_totals' LDS is read no more)
-    column_totals(rows + (size_t)nrows * 2 * ngroups, nrows, 1, nullptr, tot_t);
+    if (gate == nullptr && lrs == nullptr) return;  // (uniform; a clip comes with a rate)
+    if (clip) {
+        __syncthreads();  // (column_totals' LDS is read no more)
+        column_totals(rows + (size_t)nrows * 2 * ngroups, nrows, 1, nullptr, tot_t);
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int skipped = clip_decide(tot_t[0], clip);
+        const int skipped = clip ? clip_decide(tot_t[0], clip) : 0;
         if (gate != nullptr && !skipped) gate_rule(tot_s, gate, gate_n);
-        clip->lr = lrs->lr;
-        lr_advance(lrs);
-        clip_count(clip);
+        if (clip) clip->lr = lrs->lr;
+        if (lrs) lr_advance(lrs);
+        if (clip) clip_count(clip);
     }
 }
 
@@ -578,150 +490,176 @@ extern "C" size_t gm_group_sumsq_scratch(long long total) {
     return (size_t)nb * 2 * kMaxGroups * sizeof(double);
 }
 
-// The launch path of every entry point: shared checks, chunking, the kernel of (form, group
-// count), finalize.  mom: the buffers of upd::mom; gate: optional (null: sums only); lrs: the
-// device rate of the device-rate forms (null: h.lr, the argument).
-template <upd U>
-static auto dlr_kernel(bool few) {
-    return few ? k_group_sumsq_dlr<U, 8> : k_group_sumsq_dlr_runs<U>;
+// What an entry point asks of the launch path.
+struct pass_spec {
+    const char* entry;  // the entry's name in its messages ("group_sumsq_lr")
+    const gm_tensor* table;
+    float* const* mom;  // the buffers of upd::mom and nest
+    int nt;
+    long long total;
+    int ngroups;
+    sgdm_args h;  // (h.lr: the rate where lrs is null)
+    upd form;
+    gm_lr_state* lrs;          // the device rate (null: h.lr, the argument)
+    const gm_sgd_pgroup* pg;   // with lrs: the device group table (null: h.wd for every tensor)
+    int npg;
+    gm_clip_state* clip;       // with lrs: the sums launch, the clip's finalize, the apply launch
+    double* out;
+    void* scratch;
+    size_t scratch_bytes;
+    void* gate;  // optional (null: sums only)
+    int gate_n;
+    void* stream;
+};
+
+using kernel_t = void (*)(pass_args, const gm_tensor*, float* const*, const gm_sgd_pgroup*, double*);
+
+template <upd U, class H>
+static kernel_t fused_kernel(bool few) {
+    return few ? k_group_sumsq<U, body::few, H, false> : k_group_sumsq<U, body::runs, H, false>;
 }
 
 template <upd U>
-static auto pg_kernel(bool few) {
-    return few ? k_group_sumsq_pg<U, 8> : k_group_sumsq_pg_runs<U>;
+static kernel_t apply_kernel(bool pg) {
+    return pg ? k_group_apply<U, pgroup_args> : k_group_apply<U, uniform_args>;
 }
 
 template <upd U>
-static void launch_apply(int nb, hipStream_t st, const gm_tensor* table, float* const* mom, int nt, long long total,
-                         const sgdm_args& h, const gm_clip_state* clip, const gm_sgd_pgroup* pg, int npg,
-                         long long chunk) {
-    if (pg) k_group_apply_pg<U><<<nb, 256, 0, st>>>(table, mom, nt, total, h.gscale, clip, h.mu, pg, npg, chunk);
-    else k_group_apply<U><<<nb, 256, 0, st>>>(table, mom, nt, total, h.gscale, clip, h.mu, h.wd, chunk);
+static kernel_t table_or_not(bool pg, bool few) {
+    return pg ? fused_kernel<U, pgroup_args>(few) : fused_kernel<U, uniform_args>(few);
 }
 
-// pg (with lrs): the device group table of gm_group_sumsq_pg (null: h.wd for every tensor)
-// clip (with lrs): gm_group_sumsq_clip - the sums launch, the clip's finalize, the apply launch
-static int group_sumsq(const gm_tensor* table, float* const* mom, int nt, long long total, int ngroups,
-                       const sgdm_args& h, upd form, double* out, void* scratch, size_t scratch_bytes, void* gate,
-                       int gate_n, void* stream, gm_lr_state* lrs = nullptr, const gm_sgd_pgroup* pg = nullptr,
-                       int npg = 0, gm_clip_state* clip = nullptr) {
+// The kernel of (form, functor, body) - the fused pass, or the clipped entry's apply launch.  Null:
+// a combination no entry point asks for (a table owns a weight decay, so there is no none or sgd
+// over it; Nesterov's step without a table is the clipped entry's alone).
+static kernel_t kernel_of(upd form, bool pg, bool few, bool apply) {
+    switch (form) {
+        case upd::none:
+            return apply || pg ? nullptr : fused_kernel<upd::none, uniform_args>(few);
+        case upd::sgd:
+            return apply ? apply_kernel<upd::sgd>(pg) : (pg ? nullptr : fused_kernel<upd::sgd, uniform_args>(few));
+        case upd::decay:
+            return apply ? apply_kernel<upd::decay>(pg) : table_or_not<upd::decay>(pg, few);
+        case upd::mom:
+            return apply ? apply_kernel<upd::mom>(pg) : table_or_not<upd::mom>(pg, few);
+        case upd::nest:
+            return apply ? apply_kernel<upd::nest>(pg) : (pg ? fused_kernel<upd::nest, pgroup_args>(few) : nullptr);
+    }
+    return nullptr;
+}
+
+// The launch path of every entry point: shared checks, chunking, the kernel of (form, functor,
+// group count), finalize; for the clipped entry the sums, the finalize, the apply.
+static int group_sumsq(const pass_spec& s) {
+    const int ngroups = s.ngroups;
     // (main, bypass) groups per branch: 4 for the two-branch gate, 2 nb for the N-branch one (nb in
     // the state: the rule reads 4 nb sums)
-    GM_REQUIRE(!gate || (gate_n ? (ngroups >= 4 && ngroups % 2 == 0) : ngroups == 4),
-               "group_sumsq_gate: %d groups do not match the %s gate", ngroups, gate_n ? "N-branch" : "two-branch");
-    GM_REQUIRE(table && nt >= 1 && total >= 1, "group_sumsq: empty tensor table");
+    GM_REQUIRE(!s.gate || (s.gate_n ? (ngroups >= 4 && ngroups % 2 == 0) : ngroups == 4),
+               "group_sumsq_gate: %d groups do not match the %s gate", ngroups, s.gate_n ? "N-branch" : "two-branch");
+    GM_REQUIRE(s.table && s.nt >= 1 && s.total >= 1, "group_sumsq: empty tensor table");
     GM_REQUIRE(ngroups >= 1 && ngroups <= kMaxGroups, "group_sumsq: ngroups must be 1..%d", kMaxGroups);
     // (the total's column lies behind the rows in the scratch, which is sized for kMaxGroups)
-    GM_REQUIRE(!clip || ngroups < kMaxGroups, "group_sumsq_clip: ngroups must be 1..%d", kMaxGroups - 1);
-    GM_REQUIRE(out, "group_sumsq: null output");
-    const long long chunk = chunk_elems(total);
-    GM_REQUIRE((total + chunk - 1) / chunk < (1ll << 31), "group_sumsq: too many elements");
-    GM_REQUIRE(scratch && scratch_bytes >= gm_group_sumsq_scratch(total),
-               "group_sumsq: scratch %zu < %zu bytes", scratch_bytes, gm_group_sumsq_scratch(total));
-    const int nb = (int)((total + chunk - 1) / chunk);
-    hipStream_t st = as_stream(stream);
-    double* rows = (double*)scratch;
+    GM_REQUIRE(!s.clip || ngroups < kMaxGroups, "group_sumsq_clip: ngroups must be 1..%d", kMaxGroups - 1);
+    GM_REQUIRE(s.out, "group_sumsq: null output");
+    const long long chunk = chunk_elems(s.total);
+    GM_REQUIRE((s.total + chunk - 1) / chunk < (1ll << 31), "group_sumsq: too many elements");
+    GM_REQUIRE(s.scratch && s.scratch_bytes >= gm_group_sumsq_scratch(s.total),
+               "group_sumsq: scratch %zu < %zu bytes", s.scratch_bytes, gm_group_sumsq_scratch(s.total));
+    const int nb = (int)((s.total + chunk - 1) / chunk);
     const bool few = ngroups <= 8;  // else the N-branch gates (C5: 12 branches -> 24 groups)
-    const bool plain = form == upd::none || form == upd::sgd;
-    if (clip) {
-        const auto k = few ? k_group_sumsq_tot<8> : k_group_sumsq_tot_runs;
-        k<<<nb, 256, 0, st>>>(table, has_buffer(form) ? mom : nullptr, nt, total, ngroups, h.gscale, chunk, rows);
-        int rc = check_launch("k_group_sumsq_tot");
-        if (rc) return rc;
-        k_group_finalize_clip<<<1, kFinT, 0, st>>>(rows, nb, ngroups, out, gate, gate && gate_n ? 1 : 0, lrs, clip);
-        rc = check_launch("k_group_finalize_clip");
-        if (rc) return rc;
-        switch (form) {
-            case upd::nest: launch_apply<upd::nest>(nb, st, table, mom, nt, total, h, clip, pg, npg, chunk); break;
-            case upd::mom: launch_apply<upd::mom>(nb, st, table, mom, nt, total, h, clip, pg, npg, chunk); break;
-            case upd::decay: launch_apply<upd::decay>(nb, st, table, mom, nt, total, h, clip, pg, npg, chunk); break;
-            default: launch_apply<upd::sgd>(nb, st, table, mom, nt, total, h, clip, pg, npg, chunk); break;
-        }
-        return check_launch("k_group_apply");
-    }
-    if (pg) {
-        const auto k = form == upd::nest ? pg_kernel<upd::nest>(few)
-                                         : (form == upd::mom ? pg_kernel<upd::mom>(few) : pg_kernel<upd::decay>(few));
-        k<<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h.gscale, lrs, h.mu, pg, npg, chunk, rows);
-    } else if (lrs) {
-        const auto k = form == upd::sgd ? dlr_kernel<upd::sgd>(few)
-                                        : (form == upd::mom ? dlr_kernel<upd::mom>(few) : dlr_kernel<upd::decay>(few));
-        k<<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h.gscale, lrs, h.mu, h.wd, chunk, rows);
-    } else if (plain) {
-        const bool sgd = form == upd::sgd;
-        const auto k = few ? (sgd ? k_group_sumsq<true, 8> : k_group_sumsq<false, 8>)
-                           : (sgd ? k_group_sumsq_runs<true> : k_group_sumsq_runs<false>);
-        k<<<nb, 256, 0, st>>>(table, nt, total, ngroups, h.gscale, h.lr, chunk, rows);
-    } else {
-        const bool mo = form == upd::mom;
-        const auto k = few ? (mo ? k_group_sumsq_sgdm<true, 8> : k_group_sumsq_sgdm<false, 8>)
-                           : (mo ? k_group_sumsq_sgdm_runs<true> : k_group_sumsq_sgdm_runs<false>);
-        k<<<nb, 256, 0, st>>>(table, mom, nt, total, ngroups, h, chunk, rows);
-    }
-    int rc = check_launch(pg ? "k_group_sumsq_pg"
-                             : (lrs ? "k_group_sumsq_dlr" : (plain ? "k_group_sumsq" : "k_group_sumsq_sgdm")));
+    const kernel_t update = kernel_of(s.form, s.pg != nullptr, few, s.clip != nullptr);
+    GM_REQUIRE(update, "%s: no kernel for this update form", s.entry);
+    hipStream_t st = as_stream(s.stream);
+    double* rows = (double*)s.scratch;
+    const pass_args a{s.nt, s.total, ngroups, s.h.gscale, s.h.lr, s.h.mu, s.h.wd, s.lrs, s.npg, s.clip, chunk};
+    // the clipped entry: the sums alone first (the buffers, where the apply launch will stream
+    // them, for the 16-byte path only), and the update behind the finalize
+    const kernel_t sums = !s.clip ? update
+                                  : (few ? k_group_sumsq<upd::none, body::few, uniform_args, true>
+                                         : k_group_sumsq<upd::none, body::runs, uniform_args, true>);
+    sums<<<nb, 256, 0, st>>>(a, s.table, !s.clip || has_buffer(s.form) ? s.mom : nullptr, s.pg, rows);
+    int rc = check_launch("k_group_sumsq");
     if (rc) return rc;
-    if (lrs) k_group_finalize_lr<<<1, kFinT, 0, st>>>(rows, nb, ngroups, out, gate, gate && gate_n ? 1 : 0, lrs);
-    else k_group_finalize<<<1, kFinT, 0, st>>>(rows, nb, ngroups, out, gate, gate && gate_n ? 1 : 0);
-    return check_launch("k_group_finalize");
+    k_group_finalize<<<1, kFinT, 0, st>>>(rows, nb, ngroups, s.out, s.gate, s.gate && s.gate_n ? 1 : 0, s.lrs, s.clip);
+    rc = check_launch("k_group_finalize");
+    if (rc || !s.clip) return rc;
+    update<<<nb, 256, 0, st>>>(a, s.table, s.mom, s.pg, rows);
+    return check_launch("k_group_apply");
+}
+
+// The update's argument rules, stated once; each entry applies them under its own name.  pgroups
+// (an entry with a parameter-group table): the table owns the weight decay.
+static int check_update(const char* entry, float* const* mom, float momentum, float weight_decay, int nesterov,
+                        const gm_sgd_pgroup* pgroups, int npgroups) {
+    GM_REQUIRE(!pgroups || (npgroups >= 1 && npgroups <= GM_SGD_MAX_PGROUPS), "%s: npgroups must be 1..%d", entry,
+               GM_SGD_MAX_PGROUPS);
+    GM_REQUIRE(std::isfinite(momentum) && momentum >= 0.f, "%s: momentum must be finite and >= 0", entry);
+    GM_REQUIRE(std::isfinite(weight_decay) && weight_decay >= 0.f, "%s: weight_decay must be finite and >= 0", entry);
+    GM_REQUIRE(!pgroups || weight_decay == 0.f,
+               "%s: the parameter-group table owns the weight decay (weight_decay must be 0)", entry);
+    GM_REQUIRE(!nesterov || momentum > 0.f, "%s: nesterov requires a momentum > 0", entry);
+    GM_REQUIRE((mom != nullptr) == (momentum != 0.f),
+               "%s: momentum buffers must be given if and only if momentum != 0", entry);
+    return 0;
+}
+
+// The update form an entry's arguments ask for (after check_update)
+static upd form_of(float* const* mom, bool decay, int nesterov) {
+    return mom ? (nesterov ? upd::nest : upd::mom) : (decay ? upd::decay : upd::sgd);
 }
 
 extern "C" int gm_group_sumsq(const gm_tensor* table, int nt, long long total, int ngroups, float gscale,
                               float lr, double* out, void* scratch, size_t scratch_bytes, void* stream) {
-    return group_sumsq(table, nullptr, nt, total, ngroups, {gscale, lr, 0.f, 0.f}, lr != 0.f ? upd::sgd : upd::none,
-                       out, scratch, scratch_bytes, nullptr, 0, stream);
+    return group_sumsq({"group_sumsq", table, nullptr, nt, total, ngroups, {gscale, lr, 0.f, 0.f},
+                        lr != 0.f ? upd::sgd : upd::none, nullptr, nullptr, 0, nullptr, out, scratch, scratch_bytes,
+                        nullptr, 0, stream});
 }
 
 extern "C" int gm_group_sumsq_gate(const gm_tensor* table, int nt, long long total, int ngroups, float gscale,
                                    float lr, double* out, void* scratch, size_t scratch_bytes, void* gate,
                                    int gate_n, void* stream) {
     GM_REQUIRE(gate, "group_sumsq_gate: null gate state");
-    return group_sumsq(table, nullptr, nt, total, ngroups, {gscale, lr, 0.f, 0.f}, lr != 0.f ? upd::sgd : upd::none,
-                       out, scratch, scratch_bytes, gate, gate_n, stream);
+    return group_sumsq({"group_sumsq_gate", table, nullptr, nt, total, ngroups, {gscale, lr, 0.f, 0.f},
+                        lr != 0.f ? upd::sgd : upd::none, nullptr, nullptr, 0, nullptr, out, scratch, scratch_bytes,
+                        gate, gate_n, stream});
 }
 
 extern "C" int gm_group_sumsq_sgdm(const gm_tensor* table, float* const* mom, int nt, long long total,
                                    int ngroups, float gscale, float lr, float momentum, float weight_decay,
                                    double* out, void* scratch, size_t scratch_bytes, void* gate, int gate_n,
                                    void* stream) {
-    GM_REQUIRE(std::isfinite(momentum) && momentum >= 0.f, "group_sumsq_sgdm: momentum must be finite and >= 0");
-    GM_REQUIRE(std::isfinite(weight_decay) && weight_decay >= 0.f,
-               "group_sumsq_sgdm: weight_decay must be finite and >= 0");
-    GM_REQUIRE((mom != nullptr) == (momentum != 0.f),
-               "group_sumsq_sgdm: momentum buffers must be given if and only if momentum != 0");
-    return group_sumsq(table, mom, nt, total, ngroups, {gscale, lr, momentum, weight_decay},
-                       mom ? upd::mom : upd::decay, out, scratch, scratch_bytes, gate, gate_n, stream);
+    const char* entry = "group_sumsq_sgdm";
+    const int rc = check_update(entry, mom, momentum, weight_decay, 0, nullptr, 0);
+    if (rc) return rc;
+    // (this entry's update runs at any weight decay: 0 is the decay form with wd 0)
+    return group_sumsq({entry, table, mom, nt, total, ngroups, {gscale, lr, momentum, weight_decay},
+                        form_of(mom, true, 0), nullptr, nullptr, 0, nullptr, out, scratch, scratch_bytes, gate, gate_n,
+                        stream});
 }
 
 extern "C" int gm_group_sumsq_lr(const gm_tensor* table, float* const* mom, int nt, long long total, int ngroups,
                                  float gscale, gm_lr_state* lr, float momentum, float weight_decay, double* out,
                                  void* scratch, size_t scratch_bytes, void* gate, int gate_n, void* stream) {
-    GM_REQUIRE(lr, "group_sumsq_lr: null lr state");
-    GM_REQUIRE(std::isfinite(momentum) && momentum >= 0.f, "group_sumsq_lr: momentum must be finite and >= 0");
-    GM_REQUIRE(std::isfinite(weight_decay) && weight_decay >= 0.f,
-               "group_sumsq_lr: weight_decay must be finite and >= 0");
-    GM_REQUIRE((mom != nullptr) == (momentum != 0.f),
-               "group_sumsq_lr: momentum buffers must be given if and only if momentum != 0");
-    const upd form = mom ? upd::mom : (weight_decay != 0.f ? upd::decay : upd::sgd);
-    return group_sumsq(table, mom, nt, total, ngroups, {gscale, 0.f, momentum, weight_decay}, form, out, scratch,
-                       scratch_bytes, gate, gate_n, stream, lr);
+    const char* entry = "group_sumsq_lr";
+    GM_REQUIRE(lr, "%s: null lr state", entry);
+    const int rc = check_update(entry, mom, momentum, weight_decay, 0, nullptr, 0);
+    if (rc) return rc;
+    return group_sumsq({entry, table, mom, nt, total, ngroups, {gscale, 0.f, momentum, weight_decay},
+                        form_of(mom, weight_decay != 0.f, 0), lr, nullptr, 0, nullptr, out, scratch, scratch_bytes, gate,
+                        gate_n, stream});
 }
 
 extern "C" int gm_group_sumsq_pg(const gm_tensor* table, float* const* mom, int nt, long long total, int ngroups,
                                  float gscale, gm_lr_state* lr, const gm_sgd_pgroup* pgroups, int npgroups,
                                  float momentum, int nesterov, double* out, void* scratch, size_t scratch_bytes,
                                  void* gate, int gate_n, void* stream) {
-    GM_REQUIRE(lr, "group_sumsq_pg: null lr state");
-    GM_REQUIRE(pgroups, "group_sumsq_pg: null parameter-group table");
-    GM_REQUIRE(npgroups >= 1 && npgroups <= GM_SGD_MAX_PGROUPS, "group_sumsq_pg: npgroups must be 1..%d",
-               GM_SGD_MAX_PGROUPS);
-    GM_REQUIRE(std::isfinite(momentum) && momentum >= 0.f, "group_sumsq_pg: momentum must be finite and >= 0");
-    GM_REQUIRE(!nesterov || momentum > 0.f, "group_sumsq_pg: nesterov requires a momentum > 0");
-    GM_REQUIRE((mom != nullptr) == (momentum != 0.f),
-               "group_sumsq_pg: momentum buffers must be given if and only if momentum != 0");
-    const upd form = mom ? (nesterov ? upd::nest : upd::mom) : upd::decay;
-    return group_sumsq(table, mom, nt, total, ngroups, {gscale, 0.f, momentum, 0.f}, form, out, scratch,
-                       scratch_bytes, gate, gate_n, stream, lr, pgroups, npgroups);
+    const char* entry = "group_sumsq_pg";
+    GM_REQUIRE(lr, "%s: null lr state", entry);
+    GM_REQUIRE(pgroups, "%s: null parameter-group table", entry);
+    const int rc = check_update(entry, mom, momentum, 0.f, nesterov, pgroups, npgroups);
+    if (rc) return rc;
+    return group_sumsq({entry, table, mom, nt, total, ngroups, {gscale, 0.f, momentum, 0.f}, form_of(mom, true, nesterov),
+                        lr, pgroups, npgroups, nullptr, out, scratch, scratch_bytes, gate, gate_n, stream});
 }
 
 extern "C" int gm_group_sumsq_clip(const gm_tensor* table, float* const* mom, int nt, long long total, int ngroups,
@@ -729,23 +667,16 @@ extern "C" int gm_group_sumsq_clip(const gm_tensor* table, float* const* mom, in
                                    float momentum, float weight_decay, int nesterov, gm_clip_state* clip,
                                    double* out, void* scratch, size_t scratch_bytes, void* gate, int gate_n,
                                    void* stream) {
-    GM_REQUIRE(clip, "group_sumsq_clip: null clip state");
-    GM_REQUIRE(lr, "group_sumsq_clip: null lr state");
-    GM_REQUIRE(!pgroups || (npgroups >= 1 && npgroups <= GM_SGD_MAX_PGROUPS),
-               "group_sumsq_clip: npgroups must be 1..%d", GM_SGD_MAX_PGROUPS);
-    GM_REQUIRE(std::isfinite(momentum) && momentum >= 0.f, "group_sumsq_clip: momentum must be finite and >= 0");
-    GM_REQUIRE(std::isfinite(weight_decay) && weight_decay >= 0.f,
-               "group_sumsq_clip: weight_decay must be finite and >= 0");
-    GM_REQUIRE(!pgroups || weight_decay == 0.f,
-               "group_sumsq_clip: the parameter-group table owns the weight decay (weight_decay must be 0)");
-    GM_REQUIRE(!nesterov || momentum > 0.f, "group_sumsq_clip: nesterov requires a momentum > 0");
-    GM_REQUIRE((mom != nullptr) == (momentum != 0.f),
-               "group_sumsq_clip: momentum buffers must be given if and only if momentum != 0");
-    const upd form = mom ? (nesterov ? upd::nest : upd::mom)
-                         : ((pgroups || weight_decay != 0.f) ? upd::decay : upd::sgd);
-    return group_sumsq(table, mom, nt, total, ngroups, {gscale, 0.f, momentum, weight_decay}, form, out, scratch,
-                       scratch_bytes, gate, gate_n, stream, lr, pgroups, pgroups ? npgroups : 0, clip);
+    const char* entry = "group_sumsq_clip";
+    GM_REQUIRE(clip, "%s: null clip state", entry);
+    GM_REQUIRE(lr, "%s: null lr state", entry);
+    const int rc = check_update(entry, mom, momentum, weight_decay, nesterov, pgroups, npgroups);
+    if (rc) return rc;
+    return group_sumsq({entry, table, mom, nt, total, ngroups, {gscale, 0.f, momentum, weight_decay},
+                        form_of(mom, pgroups || weight_decay != 0.f, nesterov), lr, pgroups, pgroups ? npgroups : 0, clip,
+                        out, scratch, scratch_bytes, gate, gate_n, stream});
 }
+
 
 extern "C" int gm_clip_state_check(const gm_clip_state* host) {
     GM_REQUIRE(host, "clip_state_check: null state");

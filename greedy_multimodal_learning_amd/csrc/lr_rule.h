@@ -1,5 +1,5 @@
 // The device-resident learning rate's schedule rule (gm_lr_state, greedymml.h) as one function of
-// the pass index, shared by the host (gm_lr_at) and the device: thread 0 of k_group_finalize_lr
+// the pass index, shared by the host (gm_lr_at) and the device: thread 0 of k_group_finalize
 // (group_sumsq.hip) advances the state behind each update pass, so the rate never is a kernel
 // argument and one captured step serves every rate.  fp64 throughout, one rounding to fp32.
 #pragma once

@@ -1,5 +1,6 @@
 """One bench step as a kernel listing from a rocprofv3 kernel_trace.csv: every launch of
-the median step (steps delimited by the fused norms+SGD launch k_group_sumsq<true>) in
+the median step (steps delimited by k_group_finalize, which every form of the fused norms+SGD
+pass launches exactly once; a clipped step's apply launch falls behind the mark) in
 start order with its offset, duration, queue and grid, plus the step's concurrency
 profile (time with 0 / 1 / 2 / 3+ kernels running) and the busy time per kernel family
 split by how many other kernels ran beside it.
@@ -16,7 +17,7 @@ def family(name):
     for pat, fam in (("k_conv_halo", "conv_halo"), ("k_conv_rw", "conv_rw"), ("k_conv_stem", "conv_stem"),
                      ("k_conv_igemm", "conv_igemm"), ("k_conv_wgrad", "wgrad"), ("k_wgrad_sum", "wgrad_sum"),
                      ("k_bn_bwd", "bn_bwd"), ("k_bn_fwd", "bn_fwd"), ("k_bn_", "bn_other"), ("maxpool", "maxpool"),
-                     ("k_gemm_f32", "gemm_f32"), ("copyBuffer", "copy"), ("group_sumsq", "sgd"),
+                     ("k_gemm_f32", "gemm_f32"), ("copyBuffer", "copy"), ("group_sumsq", "sgd"), ("k_group_", "sgd"),
                      ("k_weight_prep", "wprep"), ("k_wprep", "wprep"), ("k_colreduce", "mmtm"),
                      ("k_channel_scale", "mmtm"), ("k_rowreduce", "mmtm"), ("xent", "loss")):
         if pat in n:
@@ -34,7 +35,7 @@ def main():
         grid = r.get("Grid_Size") or r.get("Grid_Size_X") or "?"
         ks.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], q, grid))
     ks.sort()
-    marks = [i for i, k in enumerate(ks) if "k_group_sumsq<true" in k[2]]
+    marks = [i for i, k in enumerate(ks) if "k_group_finalize" in k[2]]
     wins = [(a, b) for a, b in zip(marks, marks[1:]) if b > a + 1]
     if not wins:
         print("no complete step window")

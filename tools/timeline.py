@@ -1,5 +1,5 @@
 """Step timeline from a rocprofv3 kernel_trace.csv: steps are delimited by the
-per-step k_group_sumsq<true> (fused norms + SGD) launch.  For each step window
+per-step k_group_finalize launch (every form of the fused norms + SGD pass launches it exactly once).  For each step window
 prints the wall time, the union of kernel-busy time (GPU idle = wall - union),
 the summed kernel time (overlap = sum / union) and the longest idle gaps with
 the kernels either side.  usage: python tools/timeline.py kernel_trace.csv [n_gaps]"""
@@ -9,7 +9,7 @@ import sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 ngap = int(sys.argv[2]) if len(sys.argv) > 2 else 8
 ks = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in rows))
-marks = [i for i, k in enumerate(ks) if "k_group_sumsq<true>" in k[2]]
+marks = [i for i, k in enumerate(ks) if "k_group_finalize" in k[2]]
 steps = []
 for a, b in zip(marks, marks[1:]):
     win = ks[a + 1:b + 1]

@@ -2,7 +2,8 @@
 
     python tools/trace_gaps.py gpurun_out/prof_X/bench_kernel_trace.csv [--steps N] [--marker NAME]
 
-A step is delimited by the marker kernel (default: k_group_sumsq, the step's last pass).
+A step is delimited by the marker kernel (default: k_group_finalize, which every
+form of the step's last pass, the fused norms+SGD pass, launches exactly once).
 For the last N steps prints the wall time, the union of kernel intervals (busy), the idle
 gaps, the summed kernel time (overlap = summed - busy) and the largest gaps with the
 kernels on either side.
@@ -15,7 +16,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("trace")
     ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--marker", default="k_group_sumsq")
+    ap.add_argument("--marker", default="k_group_finalize")
     ap.add_argument("--top", type=int, default=12)
     a = ap.parse_args()
     rows = []

@@ -1,4 +1,4 @@
-"""Run the bench's fused norms+SGD pass (k_group_sumsq<SGD>) a few times on the C2
+"""Run the bench's fused norms+SGD pass (k_group_sumsq<upd::sgd, ...>) a few times on the C2
 model, for PMC collection (tools/gpu.sh pmcg:fetch / pmcg:write)."""
 import os
 import sys
